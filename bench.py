@@ -12,6 +12,12 @@ The post stage is fed designed pose maps (3 persons per frame) so that its cost
 is that of real footage (raw outputs of random weights produce ~4k peaks, see
 SURVEY.md §8d); the network still runs in full every step.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps
+and prints the result line; the per-op roofline fields come from HIP events on the
+last timed step itself.  `--full` adds the sub-measurements that take runs of their
+own (per-frame leg, caller path, Mode R, CPU baseline).  `--dump-outputs DIR` writes
+what the last timed step computed (dump_outputs).
+
 Multi-GPU: one process per GPU, frames sharded across ranks with no collective
 on the data path (weak scaling).  `--gpus N` without a WORLD_SIZE in the
 environment starts the N rank processes itself (islpose.parallel.spawn_ranks);
@@ -99,7 +105,18 @@ def parse(argv=None):
                    help="skip the Mode R sub-measurement (net 184x328 at batch 32 and batch 1)")
     p.add_argument("--pg-timeout", type=float, default=120.0,
                    help="seconds a gloo collective (init, barrier, gather) may block before the rank fails")
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run the sub-measurements: the per-frame leg ('frame'), the caller "
+                        "path ('e2e'), Mode R ('mode_r') and the CPU baseline ('cpu_baseline'); --frame-count, "
+                        "--e2e-steps, --no-mode-r, --no-cpu and --cpu-frames select among them.  Without --full "
+                        "only the headline's own warmup and timed steps run")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                        "(see dump_outputs)")
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def rank_env():
@@ -390,15 +407,20 @@ def gpu_main(args, rank, local, world):
     # one GPU: the per-frame leg first, on a fresh process -- after the batch-32 legs (their
     # arenas, Mode R's 200 timed batch-1 steps) the same leg read 3-6 % lower (171-177 vs
     # 182 frames/s alone, profiles/r06/fr6/); the headline's timed steps do not depend on it
-    frame_first = args.frame_count > 0 and world == 1
+    # (the sub-measurements -- frame leg, e2e, Mode R, CPU baseline -- run only with --full)
+    want_frame = args.full and args.frame_count > 0
+    frame_first = want_frame and world == 1
     frame = frame_leg(args) if frame_first else None
     m = measure(args.scale, B, args.steps, args.warmup, S, not args.no_op_timing)
-    e2e = e2e_rate(args, m["lanes"][0].est, m["frames_h"], m["maps"], dev) if args.e2e_steps > 0 else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m, rank, dev)
+    e2e = e2e_rate(args, m["lanes"][0].est, m["frames_h"], m["maps"], dev) \
+        if args.full and args.e2e_steps > 0 else None
     # Mode R (the reference scripts' net size, scale_search=[0.5], body.py:41): the
     # same step at batch 32 and at batch 1 (the scripts' one-frame-per-call pattern), in the
     # same invocation, with their own roofline -- a sub-object, not the headline value
     mode_r = None
-    if args.mode_r and args.scale == 1.0 and not args.no_op_timing:
+    if args.full and args.mode_r and args.scale == 1.0 and not args.no_op_timing:
         mode_r = {}
         for key, bb, st, wu in (("batch32", 32, args.steps, max(1, args.warmup)),
                                 # (batch 1: 200 timed steps, ~0.35 s, so that one host hiccup does not
@@ -438,6 +460,7 @@ def gpu_main(args, rank, local, world):
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "full": bool(args.full),
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -467,12 +490,61 @@ def gpu_main(args, rank, local, world):
         "e2e": e2e,
         "cpu_baseline": None,
     }
-    if args.frame_count > 0:
+    if want_frame:
         out["frame"] = frame if frame_first else frame_leg(args)
-    if not args.no_cpu and args.cpu_frames > 0 and world == 1:
+    if args.full and not args.no_cpu and args.cpu_frames > 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline(args, mult, nh, nw)
     print(json.dumps(out))
     sys.stdout.flush()
+
+
+DUMP_BUDGET_BYTES = 60 << 20    # --dump-outputs writes less than 64 MB in all
+
+
+def dump_outputs(path, m, rank, dev):
+    """--dump-outputs DIR: what the headline's last timed step computed, as .npy files.
+
+    candidate.npy  float64 [sum N, 5]  (frame, x, y, score, id): every frame's peaks, decoded
+                                       from the result records the step copied to the host
+    subset.npy     float64 [sum P, 28] (frame, 25 part ids, score, parts): every frame's persons
+    net_paf.npy    float32 [n, 52, h/8, w/8]  the network's outputs of the step's frames.  The
+    net_heat.npy   float32 [n, 26, h/8, w/8]  timed step leaves them in the net's arena, so they are
+                                       brought out by one more preprocess + run of the same kernels
+                                       on the same frames after the timed region; n = the first
+                                       frames that fit the size budget (all 32 at the default shape)
+    The frames, weights and designed maps are seeded, so the same arguments give the same
+    inputs in every run.  Rank r > 0 writes <name>.rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    lanes, nh, nw, mult = m["lanes"], m["nh"], m["nw"], m["mult"]
+    cand, sub, f0 = [], [], 0
+    for ln in lanes:
+        for f, r in enumerate(ln.est.decode(ln.h_res.numpy(), ln.lay, ln.est.caps, ln.b, details=False)):
+            for rows, dst in ((r.candidate, cand), (r.subset, sub)):
+                if rows.size:
+                    dst.append(np.concatenate([np.full((len(rows), 1), float(f0 + f)), rows], axis=1))
+        f0 += ln.b
+    est = lanes[0].est
+    per_frame = (est.npaf + est.njoint) * (nh // 8) * (nw // 8) * 4
+    keep = max(1, min(m["B"], DUMP_BUDGET_BYTES // per_frame))
+    pafs, heats, f0 = [], [], 0
+    for ln in lanes:
+        paf = torch.empty((ln.b, est.npaf, nh // 8, nw // 8), device=dev)
+        heat = torch.empty((ln.b, est.njoint, nh // 8, nw // 8), device=dev)
+        ln.net.preprocess(ln.frames, mult, stream=ln.stream)
+        ln.net.run(paf, heat, stream=ln.stream)
+        ln.stream.synchronize()
+        assert ln.net.range_ok(), "split-fp16 range exceeded in the dump run"
+        n = max(0, min(ln.b, keep - f0))
+        pafs.append(paf[:n].cpu().numpy())
+        heats.append(heat[:n].cpu().numpy())
+        f0 += ln.b
+    arrays = {"candidate": np.concatenate(cand) if cand else np.zeros((0, 5)),
+              "subset": np.concatenate(sub) if sub else np.zeros((0, est.njoint + 2)),
+              "net_paf": np.concatenate(pafs), "net_heat": np.concatenate(heats)}
+    sfx = ".rank%d" % rank if rank else ""
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(path, name + sfx + ".npy"), a)
 
 
 def frame_leg(args):

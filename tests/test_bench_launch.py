@@ -40,6 +40,25 @@ def test_bench_single_rank_dry_run():
     assert out["n_gpus"] == 1 and out["shards"] == [[0, 2]]
 
 
+def test_bench_options_full_and_dump_outputs():
+    """A plain run has the sub-measurements off; --full and --dump-outputs DIR parse, and the
+    selectors of the sub-measurements keep their defaults under --full."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "somewhere"])
+    assert a.full and a.dump_outputs == "somewhere"
+    assert a.frame_count > 0 and a.e2e_steps > 0 and a.mode_r and not a.no_cpu
+
+
+def test_bench_rejects_zero_steps():
+    r = _run("--dry-run", "--steps", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_bench_rejects_world_mismatch():
     e = _env()
     e.update(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")

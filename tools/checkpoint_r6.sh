@@ -7,7 +7,7 @@ rc=$?
 tail -3 $O/gputest.log
 if [ $rc -ne 0 ]; then grep -E "FAIL|Error|error" $O/gputest.log | head -20; echo "pytest rc=$rc: stopping"; exit $rc; fi
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 &&
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err &&
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err &&
 timeout -k 10 600 python3 tools/bench_configs.py --config c3 > $O/c3.json 2>> $O/cfg.err &&
 timeout -k 10 600 python3 tools/bench_configs.py --config c4 > $O/c4.json 2>> $O/cfg.err &&
 timeout -k 10 600 python3 tools/bench_configs.py --config c5 > $O/c5.json 2>> $O/cfg.err

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 T=${1:-r6p}; O=gpurun_out/$T; mkdir -p $O
 B="python3 bench.py --no-cpu --no-mode-r --e2e-steps 0 --frame-count 0 --steps 3 --warmup 1"
 R="python3 bench.py --no-cpu --no-mode-r --e2e-steps 0 --frame-count 0 --steps 3 --warmup 1 --scale 0.5"
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err &&
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- $B > $O/trace.log 2>&1 &&
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o run -- $B > $O/fetch.log 2>&1 &&
 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o run -- $B > $O/write.log 2>&1 &&
