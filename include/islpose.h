@@ -55,6 +55,18 @@ enum isl_status {
  *   ISL_ALGO_DIRECT every conv as a direct implicit GEMM on the FP32 matrix cores. */
 enum isl_algo { ISL_ALGO_X3 = 0, ISL_ALGO_WINO = 1, ISL_ALGO_DIRECT = 2 };
 
+/* Precision of the ISL_ALGO_X3 convolutions (not in the reference):
+ *   ISL_PREC_FP32   three fp16 products per multiply-add, fp32-accurate -- the default,
+ *                   bit for bit what the library computed before this switch existed;
+ *   ISL_PREC_FP16   one fp16 product per multiply-add: the activations are rounded to
+ *                   fp16 (round to nearest even) once when a kernel stages them, the
+ *                   filters are packed as their fp16 roundings (the same per-layer 2^s),
+ *                   accumulation stays fp32 in the same K order.  A third of the matrix
+ *                   work and half the operand bytes; the maps carry ~2e-3 of their
+ *                   maximum in error instead of ~2e-6.  Opt-in.
+ * Under ISL_ALGO_WINO / ISL_ALGO_DIRECT the value is stored and has no effect. */
+enum isl_precision { ISL_PREC_FP32 = 0, ISL_PREC_FP16 = 1 };
+
 typedef struct isl_net isl_net;
 
 int isl_abi_version(void);
@@ -127,6 +139,17 @@ int isl_net_arena_info(const isl_net* net, int64_t* bytes, int* n_arenas);
 int isl_net_set_algo(isl_net* net, int algo);
 int isl_net_get_algo(const isl_net* net);
 
+/* Select the precision of a net's ISL_ALGO_X3 convs (default ISL_PREC_FP32, or the env
+ * ISLPOSE_PRECISION=fp32|fp16 at create time); any other value -> ISL_E_ARG.  The hi-only
+ * filters of ISL_PREC_FP16 are packed on the first run that needs them after a weight
+ * upload and kept, so switching back and forth repacks nothing.  The range guard is
+ * unchanged: an fp16-mode epilogue still flags |v| >= 65504, isl_net_check* still reports
+ * ISL_E_RANGE, and the caller recomputes with ISL_ALGO_DIRECT.  Captured graphs
+ * (isl_net_set_graph) are keyed by the precision.  isl_net_timing keeps kind 3 for these
+ * launches and reports the FLOPs they execute (one product per multiply-add). */
+int isl_net_set_precision(isl_net* net, int precision);
+int isl_net_get_precision(const isl_net* net);
+
 /* K ranges of the ISL_ALGO_X3 convolutions (latency of small grids such as batch-1
  * frames; not in the reference, whose torch conv runs per frame):
  *   mode 1 (default)  canonical ranges: layers of <= 1024 pixels per frame (Mode R's
@@ -195,7 +218,7 @@ int isl_net_timing(isl_net* net, int max_ops, int* n_ops, int* n_runs, double* o
 /* Diagnostic: the ops of the net's graph (convs by their caffe layer name, pools as
  * "maxpool2") and, for the last isl_net_run / isl_net_forward, which conv kernel variant
  * each ran: for ISL_ALGO_X3 convs the variant code of csrc/internal.h x3_variant_code
- * (VAR bits: 512 row union, 1024 in-block K ranges, 2048 split-K, 4096 two pairs per
+ * (VAR bits: 2 one-term fp16 products (ISL_PREC_FP16), 512 row union, 1024 in-block K ranges, 2048 split-K, 4096 two pairs per
  * step, 8192 folds its producers' split-K partials, 32768 pooled-input staging, 65536 one
  * input buffer, 131072 16x16x32 row union, 262144 conv1_1 kernel, 524288 split-K partials
  * left to its consumers (no reduce launch);

@@ -39,6 +39,10 @@
 // accumulator tiles x 3 MFMAs.
 //
 // Variants (template VAR bits):
+//   2     one-term fp16 products (isl_net_set_precision ISL_PREC_FP16, opt-in): x*w ~= x_hi*w_hi alone,
+//         one MFMA per tap; every layout below loses its [hi|lo] dimension (hi-only weight slabs,
+//         inputs rounded once at staging), everything else -- tiles, K order, ranges, epilogue and
+//         range check -- is the variant's; combines with every bit but 16 and 131072;
 //   512   row union (3x3 on 512-pixel tiles): the three kernel rows of a chunk pair
 //         are staged once as one run, a third per ky step, by loader waves, while
 //         DMA waves stream the weights (role split, see the union loop);
@@ -160,6 +164,18 @@ __device__ __forceinline__ void x3_split8(const f32x4& a, const f32x4& b, f16x8&
   }
 }
 
+// the hi half alone (ISL_PREC_FP16): the same packed RNE conversions, no residual
+__device__ __forceinline__ f16x8 x3_hi8(const f32x4& a, const f32x4& b) {
+  f16x8 hi;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const f32x2 x = k < 2 ? f32x2{a[2 * k], a[2 * k + 1]} : f32x2{b[2 * k - 4], b[2 * k - 3]};
+    const f16x2 h = __builtin_convertvector(x, f16x2);
+    hi[2 * k] = h.x; hi[2 * k + 1] = h.y;
+  }
+  return hi;
+}
+
 // Split-K reduction: the ranges' sums added in range order (the order of the in-block
 // ranges, so both give the same bits), then the epilogue of conv_x3_f16 (x 2^-s,
 // bias, activation, range check, masked stores).  One thread per (frame, chunk, pixel,
@@ -262,10 +278,15 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
   // VAR 4096 (1x1 layers, 256-channel tiles): two chunk pairs per K step
   constexpr int PPS = (VAR & 4096) ? 2 : 1;
   static_assert(PPS == 1 || KS <= 3, "two pairs per step: 1x1 / 3x3 layers");
-  constexpr int WSLAB1 = KS * 2 * 2 * BCO;       // one pair: [kx][hi|lo][h][BCO]
+  // VAR 2: one-term fp16 products (ISL_PREC_FP16): the operands are their hi halves alone --
+  // hi-only weight slabs (pack_hi_only), inputs rounded once at staging, one MFMA per tap; no lo
+  // plane is packed, fetched or staged (NH operand planes instead of two)
+  constexpr bool F16 = (VAR & X3V_F16) != 0;
+  constexpr int NH = F16 ? 1 : 2;
+  constexpr int WSLAB1 = KS * NH * 2 * BCO;      // one pair: [kx][hi|lo][h][BCO]
   constexpr int WSLAB = PPS * WSLAB1;            // 16-byte units per step
   constexpr int SEGP = SEGMAX + 1;               // + one dummy slot idle staging items write to
-  constexpr int XSLAB = 2 * 2 * PPS * SEGP;      // 16-byte units: [hi|lo][chunk of the step][px]
+  constexpr int XSLAB = NH * 2 * PPS * SEGP;     // 16-byte units: [hi|lo][chunk of the step][px]
   constexpr int BUF = WSLAB + XSLAB;
   constexpr int IT = (2 * PPS * SEGMAX + NTG - 1) / NTG; // staging items (chunk, px) per thread of a group
   static_assert(WSLAB % 64 == 0, "weight slab is whole 1 KiB DMA pieces");
@@ -273,6 +294,7 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
   constexpr bool UNION = (VAR & 512) != 0;
   // VAR 131072: the row-union loop on v_mfma_f32_16x16x32_f16 (see the M16 loop below)
   constexpr bool M16 = (VAR & 131072) != 0;
+  static_assert(!F16 || !M16, "one-term products: the 32x32x16 loops");
   static_assert(!M16 || (UNION && KS == 3 && WAVES_M == 2 && WAVES_N == 8 && WM == 2 && WN == 2),
                 "16x16x32 form: the 128-channel row-union block (16 waves of 64co x 64px)");
   // VAR 65536: one input buffer (two barriers per step) so that a wider pixel tile fits
@@ -280,7 +302,7 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
   // is amortised over 1.5x the pixels)
   constexpr bool SIB = (VAR & 65536) != 0;
   constexpr int SEGUP = x3_segu_max() + 1;       // + dummy slot
-  constexpr int XSLABU = 2 * 2 * SEGUP;          // [hi|lo][h][px]
+  constexpr int XSLABU = NH * 2 * SEGUP;         // [hi|lo][h][px]
   constexpr int SMEM0 = UNION ? 2 * WSLAB + 2 * XSLABU : SIB ? 2 * WSLAB + XSLAB
                       : (VAR & 128) ? 3 * WSLAB + 2 * XSLAB : NG * 2 * BUF;
   static_assert(!(SIB && UNION), "one input buffer: generic loop only");
@@ -289,7 +311,11 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
   constexpr bool FUSE67 = (VAR & 16) != 0;
   constexpr int F7_ROWS = 68;                    // 64 rows + 4 (staggers the banks of the pixel rows)
   constexpr int F7_SMEM = FUSE67 ? ((2 * BCO + 128) * 4 + WAVES_M * WAVES_N * 32 * F7_ROWS * 4 + 15) / 16 : 0;
-  constexpr int SMEM = SMEM0 > F7_SMEM ? SMEM0 : F7_SMEM;
+  // VAR 32: the second K group's sums cross to the first through LDS after the loop (64 KiB for
+  // 8 waves of 64co x 32px: more than the one-term form's four buffers of a 1x1 layer)
+  constexpr int G2_SMEM = G2 ? NWAVES * WM * WN * 16 * 64 * 4 / 16 : 0;
+  constexpr int SMEM1 = SMEM0 > F7_SMEM ? SMEM0 : F7_SMEM;
+  constexpr int SMEM = SMEM1 > G2_SMEM ? SMEM1 : G2_SMEM;
   static_assert(SMEM * 16 <= 160 * 1024, "LDS");
   constexpr bool RANGED = (VAR & 1024) != 0;
   constexpr bool SPLIT = (VAR & 2048) != 0;
@@ -312,6 +338,7 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
   static_assert(!(FOLD && (VIN || UNION || M16 || KS > 3 || PPS > 1)), "fold: the generic loop of 1x1 / 3x3 layers");
   static_assert(!(UNION && (RANGED || SPLIT)), "K ranges run on the generic loop");
   static_assert(PPS == 1 || !(UNION || M16 || HALFCO || DEEP || FOLD || VIN), "two pairs per step: generic loop");
+  static_assert(!F16 || !(VAR & 16), "one-term products: the fused 1x1 pair is not built (the plan runs it unfused)");
   static_assert(!G2 || (RANGED && !SPLIT && !UNION && !M16 && !SIB && !DEEP && !FOLD && !VIN && !HALFCO && PPS == 1 &&
                         !FUSE67 && !STAMP),
                 "two K groups: in-block K ranges on the plain generic loop");
@@ -387,11 +414,11 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
   const bool wave_live = !SKIP_DEAD || m0 + (wave_u / WAVES_M) * WN * 32 <= mlast;   // (uniform)
   auto tap = [&](const f16x8* sw, const f16x8* sx, int sx_plane, int kx) __attribute__((always_inline)) {
     if (SKIP_DEAD && !wave_live) return;
-    f16x8 A[WM][2], B[WN][2];
+    f16x8 A[WM][NH], B[WN][NH];
 #pragma unroll
-    for (int hl = 0; hl < 2; ++hl) {
+    for (int hl = 0; hl < NH; ++hl) {
 #pragma unroll
-      for (int wm = 0; wm < WM; ++wm) A[wm][hl] = sw[(kx * 2 + hl) * 2 * BCO + wm * 32];
+      for (int wm = 0; wm < WM; ++wm) A[wm][hl] = sw[(kx * NH + hl) * 2 * BCO + wm * 32];
 #pragma unroll
       for (int wn = 0; wn < WN; ++wn) B[wn][hl] = sx[hl * 2 * sx_plane + rel[wn] + kx];
     }
@@ -400,8 +427,10 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
 #pragma unroll
       for (int wn = 0; wn < WN; ++wn) {
         acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][0], B[wn][0], acc[wm][wn], 0, 0, 0);
-        acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][0], B[wn][1], acc[wm][wn], 0, 0, 0);
-        acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][1], B[wn][0], acc[wm][wn], 0, 0, 0);
+        if constexpr (!F16) {
+          acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][0], B[wn][NH - 1], acc[wm][wn], 0, 0, 0);
+          acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][NH - 1], B[wn][0], acc[wm][wn], 0, 0, 0);
+        }
       }
   };
 
@@ -665,11 +694,17 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
       // a missing odd chunk stages the last real chunk again (load_c clamps): its packed
       // weights are zero (pack_x3), and the staged values are finite (range-checked), so
       // it adds exact zeros
-      f16x8 hi, lo;
-      x3_split8(ru[0], ru[1], hi, lo);
-      const int px = c_px[ky] < 0 ? SEGUP - 1 : c_px[ky];   // idle items: the dummy slot
-      sx[(0 * 2 + c_ih[ky]) * SEGUP + px] = hi;
-      sx[(1 * 2 + c_ih[ky]) * SEGUP + px] = lo;
+      if constexpr (F16) {
+        const f16x8 hi = x3_hi8(ru[0], ru[1]);
+        const int px = c_px[ky] < 0 ? SEGUP - 1 : c_px[ky];
+        sx[c_ih[ky] * SEGUP + px] = hi;
+      } else {
+        f16x8 hi, lo;
+        x3_split8(ru[0], ru[1], hi, lo);
+        const int px = c_px[ky] < 0 ? SEGUP - 1 : c_px[ky];   // idle items: the dummy slot
+        sx[(0 * 2 + c_ih[ky]) * SEGUP + px] = hi;
+        sx[(1 * 2 + c_ih[ky]) * SEGUP + px] = lo;
+      }
     };
     auto issue_c = [&](int t, int bw) __attribute__((always_inline)) {
       const f16x8* src = a.wpk + ((size_t)co_t * T + t) * WSLAB;
@@ -843,10 +878,14 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
 #pragma unroll
       for (int i = 0; i < IT; ++i) {
         if (ipx[i] < 0) continue;
-        f16x8 hi, lo;
-        x3_split8(raw[i][0], raw[i][1], hi, lo);
-        s[(0 * 2 * PPS + ih[i]) * SEGP + ipx[i]] = hi;
-        s[(1 * 2 * PPS + ih[i]) * SEGP + ipx[i]] = lo;
+        if constexpr (F16) {
+          s[ih[i] * SEGP + ipx[i]] = x3_hi8(raw[i][0], raw[i][1]);
+        } else {
+          f16x8 hi, lo;
+          x3_split8(raw[i][0], raw[i][1], hi, lo);
+          s[(0 * 2 * PPS + ih[i]) * SEGP + ipx[i]] = hi;
+          s[(1 * 2 * PPS + ih[i]) * SEGP + ipx[i]] = lo;
+        }
       }
     };
     auto issue_w = [&](int t, int buf) __attribute__((always_inline)) {
@@ -983,11 +1022,17 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
         f16x8* sx = xbuf(xb);
 #pragma unroll
         for (int k = 0; k < ITL; ++k) {
-          f16x8 hi, lo;
-          x3_split8(rs[sl][k][0], rs[sl][k][1], hi, lo);
-          const int px = lpx[k] < 0 ? SEGP - 1 : lpx[k];
-          sx[(0 * 2 + lih[k]) * SEGP + px] = hi;
-          sx[(1 * 2 + lih[k]) * SEGP + px] = lo;
+          if constexpr (F16) {
+            const f16x8 hi = x3_hi8(rs[sl][k][0], rs[sl][k][1]);
+            const int px = lpx[k] < 0 ? SEGP - 1 : lpx[k];
+            sx[lih[k] * SEGP + px] = hi;
+          } else {
+            f16x8 hi, lo;
+            x3_split8(rs[sl][k][0], rs[sl][k][1], hi, lo);
+            const int px = lpx[k] < 0 ? SEGP - 1 : lpx[k];
+            sx[(0 * 2 + lih[k]) * SEGP + px] = hi;
+            sx[(1 * 2 + lih[k]) * SEGP + px] = lo;
+          }
         }
       };
       auto dissue = [&](int t, int wb) __attribute__((always_inline)) {
@@ -1373,15 +1418,21 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
 // ---------------------------------------------------------------------------
 constexpr int RGB_BCO = 64, RGB_TILE = 256;
 
+// fp16 products per MAC a launch executes: three (fp32-accurate), one under ISL_PREC_FP16
+static double x3_products(const ConvLaunch& c) { return c.f16 ? 1.0 : 3.0; }
+
 // the variant of the last conv_x3 / conv_x3_rgb launch of this thread (x3_last_variant)
 static thread_local int t_last_variant = 0;
 int x3_last_variant() { return t_last_variant; }
 
-template <int RGB_BPX>
+// F16 (ISL_PREC_FP16): one-term products -- hi-only filters [kk][h][64][8] (pack_hi_only of pack_x3_rgb) and an
+// im2col tile of the hi halves alone
+template <int RGB_BPX, bool F16>
 __global__ void __launch_bounds__(RGB_BPX, 1) conv_x3_rgb(X3Args a) {
   constexpr int RGB_NT = RGB_BPX;
-  __shared__ f16x8 s_x[2][4][RGB_BPX];          // [hi|lo][k chunk q][px]
-  __shared__ f16x8 s_w[2][2][2][RGB_BCO];        // [kk][hi|lo][h][co]
+  constexpr int NH = F16 ? 1 : 2;
+  __shared__ f16x8 s_x[NH][4][RGB_BPX];         // [hi|lo][k chunk q][px]
+  __shared__ f16x8 s_w[2][NH][2][RGB_BCO];       // [kk][hi|lo][h][co]
   __shared__ float s_b[2 * RGB_BCO];             // bias, PReLU slope
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, l32 = lane & 31;
@@ -1394,7 +1445,7 @@ __global__ void __launch_bounds__(RGB_BPX, 1) conv_x3_rgb(X3Args a) {
   const int HW = a.H * a.W, m0 = pt * RGB_BPX, mlast = min(m0 + RGB_BPX, HW) - 1;
   const int Wi = a.W + 2 * a.in_pad;
   const float* in_f = a.in + (size_t)n * a.in_fs;
-  for (int i = tid; i < 2 * 2 * 2 * RGB_BCO; i += RGB_NT) (&s_w[0][0][0][0])[i] = a.wpk[i];
+  for (int i = tid; i < 2 * NH * 2 * RGB_BCO; i += RGB_NT) (&s_w[0][0][0][0])[i] = a.wpk[i];
   for (int i = tid; i < RGB_BCO; i += RGB_NT) {
     s_b[i] = a.bias[i];
     s_b[RGB_BCO + i] = a.act == ACT_PRELU ? a.slope[i] : 0.f;
@@ -1417,7 +1468,7 @@ __global__ void __launch_bounds__(RGB_BPX, 1) conv_x3_rgb(X3Args a) {
         const int k = 9 * ky + 3 * kx + c;
         const _Float16 hi = (_Float16)v[c];
         put(0, k, px, hi);
-        put(1, k, px, (_Float16)(v[c] - (float)hi));
+        if constexpr (!F16) put(1, k, px, (_Float16)(v[c] - (float)hi));
       }
     }
   }
@@ -1425,7 +1476,7 @@ __global__ void __launch_bounds__(RGB_BPX, 1) conv_x3_rgb(X3Args a) {
 #pragma unroll
     for (int k = 27; k < 32; ++k) {
       put(0, k, px, (_Float16)0.f);
-      put(1, k, px, (_Float16)0.f);
+      if constexpr (!F16) put(1, k, px, (_Float16)0.f);
     }
   __syncthreads();
   f32x16 acc[2][2];
@@ -1437,9 +1488,9 @@ __global__ void __launch_bounds__(RGB_BPX, 1) conv_x3_rgb(X3Args a) {
       for (int r = 0; r < 16; ++r) acc[wm][wn][r] = 0.f;
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk) {
-    f16x8 A[2][2], B[2][2];
+    f16x8 A[2][NH], B[2][NH];
 #pragma unroll
-    for (int hl = 0; hl < 2; ++hl) {
+    for (int hl = 0; hl < NH; ++hl) {
 #pragma unroll
       for (int wm = 0; wm < 2; ++wm) A[wm][hl] = s_w[kk][hl][h][wm * 32 + l32];
 #pragma unroll
@@ -1450,8 +1501,10 @@ __global__ void __launch_bounds__(RGB_BPX, 1) conv_x3_rgb(X3Args a) {
 #pragma unroll
       for (int wn = 0; wn < 2; ++wn) {
         acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][0], B[wn][0], acc[wm][wn], 0, 0, 0);
-        acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][0], B[wn][1], acc[wm][wn], 0, 0, 0);
-        acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][1], B[wn][0], acc[wm][wn], 0, 0, 0);
+        if constexpr (!F16) {
+          acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][0], B[wn][NH - 1], acc[wm][wn], 0, 0, 0);
+          acc[wm][wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][NH - 1], B[wn][0], acc[wm][wn], 0, 0, 0);
+        }
       }
   }
   // epilogue (as conv_x3_f16's): x 2^-s, bias, activation, range check, float4 stores
@@ -1525,13 +1578,14 @@ hipError_t launch_conv_x3_rgb(const ConvLaunch& c, hipStream_t s) {
   const long long nb = (long long)c.n * a.px_tiles;
   if (nb <= 0 || nb > 0x7fffffff) { set_error("conv_x3_rgb: bad grid"); return hipErrorInvalidValue; }
   a.nblocks = (int)nb;
-  t_last_variant = x3_variant_code(X3V_RGB, 3, bpx, RGB_BCO);
-  hipLaunchKernelGGL(conv_x3_rgb<bpx>, dim3(a.nblocks), dim3(bpx), 0, s, a);
+  t_last_variant = x3_variant_code(X3V_RGB | (c.f16 ? X3V_F16 : 0), 3, bpx, RGB_BCO);
+  if (c.f16) hipLaunchKernelGGL((conv_x3_rgb<bpx, true>), dim3(a.nblocks), dim3(bpx), 0, s, a);
+  else hipLaunchKernelGGL((conv_x3_rgb<bpx, false>), dim3(a.nblocks), dim3(bpx), 0, s, a);
   return hipGetLastError();
 }
 
 double conv_x3_rgb_mfma_flops(const ConvLaunch& c) {
-  return 3.0 * 2.0 * RGB_BCO * 32.0 * (double)((c.H * c.W + RGB_TILE - 1) / RGB_TILE) * RGB_TILE * c.n;
+  return x3_products(c) * 2.0 * RGB_BCO * 32.0 * (double)((c.H * c.W + RGB_TILE - 1) / RGB_TILE) * RGB_TILE * c.n;
 }
 
 __global__ void __launch_bounds__(256) x3_splitk_reduce(X3Args a) {
@@ -1563,9 +1617,12 @@ __global__ void __launch_bounds__(256) x3_splitk_reduce(X3Args a) {
 // lo*hi, from zero, a missing odd chunk as zeros (the generic loop) -- the range sums meet in
 // LDS and are added in x3_canonical_order, then the epilogue of x3_splitk_reduce: the same bits
 // as the split-K launches and as the in-block ranges of larger batches, in one launch.
-template <int KS, int WN, int DEPTH>
+// F16 (ISL_PREC_FP16): one-term products -- the hi fragments of the hi-only slabs, the input chunk
+// rounded once, one MFMA per tap; the same ranges, K order and epilogue.
+template <int KS, int WN, int DEPTH, bool F16>
 __global__ void __launch_bounds__(512) conv_x3_wr(X3Args a) {
   constexpr int P = KS / 2;
+  constexpr int NH = F16 ? 1 : 2;
   constexpr int TP = KS * KS;                     // taps per chunk pair
   const int S = a.ksplit;                         // waves = K ranges
   int bid = blockIdx.x;
@@ -1597,21 +1654,21 @@ __global__ void __launch_bounds__(512) conv_x3_wr(X3Args a) {
   const int pps = (a.pairs + S - 1) / S;
   const int c2a = wave * pps, c2b = min(a.pairs, c2a + pps);
   const int U = (c2b - c2a) * TP;
-  const int BCO = a.bco_pack, WS1 = KS * 4 * BCO;
+  const int BCO = a.bco_pack, WS1 = KS * NH * 2 * BCO;
   const int co0 = co_t * 32, cpk = co0 / BCO;
   const f16x8* wb = a.wpk + (size_t)cpk * a.pairs * KS * WS1 + h * BCO + (co0 - cpk * BCO) + l32;
 
-  f16x8 A[DEPTH][2];
+  f16x8 A[DEPTH][NH];
   f32x4 B[DEPTH][WN][2];
   // tap u of the range -> its operands; past the end the last tap is read again (every load
   // unconditional: the same count in flight on every path, so the waits stay counted)
-  auto load = [&](int u, f16x8 (&Ad)[2], f32x4 (&Bd)[WN][2]) __attribute__((always_inline)) {
+  auto load = [&](int u, f16x8 (&Ad)[NH], f32x4 (&Bd)[WN][2]) __attribute__((always_inline)) {
     u = min(u, U - 1);
     const int pr = u / TP, r = u - pr * TP, ky = r / KS, kx = r - ky * KS;
     const int c2 = c2a + pr;
-    const f16x8* w = wb + (size_t)(c2 * KS + ky) * WS1 + kx * 4 * BCO;
+    const f16x8* w = wb + (size_t)(c2 * KS + ky) * WS1 + kx * NH * 2 * BCO;
     Ad[0] = w[0];
-    Ad[1] = w[2 * BCO];
+    if constexpr (!F16) Ad[NH - 1] = w[2 * BCO];
     const int c = min(2 * c2 + h, a.cin_chunks - 1);
     const float* src = in_f + (size_t)c * a.in_chs + (size_t)(ky * Wi + kx) * 8;
 #pragma unroll
@@ -1644,17 +1701,22 @@ __global__ void __launch_bounds__(512) conv_x3_wr(X3Args a) {
   const int co_e = min(co0 + 8 * (wave & 3) + 4 * h, a.cout - 1) & ~3;
   const f32x4 bias_e = *(const f32x4*)(a.bias + co_e);
   const f32x4 slope_e = a.act == ACT_PRELU ? *(const f32x4*)(a.slope + co_e) : f32x4{0.f, 0.f, 0.f, 0.f};
-  auto compute = [&](int u, const f16x8 (&Ad)[2], const f32x4 (&Bd)[WN][2]) __attribute__((always_inline)) {
+  auto compute = [&](int u, const f16x8 (&Ad)[NH], const f32x4 (&Bd)[WN][2]) __attribute__((always_inline)) {
     const int pr = u / TP;
     const bool real = 2 * (c2a + pr) + h < a.cin_chunks;   // a missing odd chunk: zeros
 #pragma unroll
     for (int wn = 0; wn < WN; ++wn) {
-      f16x8 bh, bl;
       const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-      x3_split8(real ? Bd[wn][0] : z, real ? Bd[wn][1] : z, bh, bl);
-      acc[wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ad[0], bh, acc[wn], 0, 0, 0);
-      acc[wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ad[0], bl, acc[wn], 0, 0, 0);
-      acc[wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ad[1], bh, acc[wn], 0, 0, 0);
+      if constexpr (F16) {
+        const f16x8 bh = x3_hi8(real ? Bd[wn][0] : z, real ? Bd[wn][1] : z);
+        acc[wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ad[0], bh, acc[wn], 0, 0, 0);
+      } else {
+        f16x8 bh, bl;
+        x3_split8(real ? Bd[wn][0] : z, real ? Bd[wn][1] : z, bh, bl);
+        acc[wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ad[0], bh, acc[wn], 0, 0, 0);
+        acc[wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ad[0], bl, acc[wn], 0, 0, 0);
+        acc[wn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ad[NH - 1], bh, acc[wn], 0, 0, 0);
+      }
     }
   };
   // Slot d's loads are issued in slot order (sched_barrier: the scheduler must not reorder them
@@ -2216,59 +2278,61 @@ static X3Ranges x3_ranges(const ConvLaunch& c) {
   return r;
 }
 
-template <int KS>
+// FV: X3V_F16 for the one-term form of every variant (ISL_PREC_FP16: the same plan, tiles and K
+// order on hi-only operands), 0 for the three-term kernels
+template <int KS, int FV>
 static hipError_t launch_ks(const ConvLaunch& c, hipStream_t s) {
   if constexpr (KS == 3) {
     if (x3_big_tiles(c) && x3_union(c)) {
 #ifdef ISLPOSE_DEV
       if (x3_union_mode() == 4 && c.dbg) {   // development build only (tools/convbench)
         switch (c.bco) {
-          case 128: return launch_t<KS, 2, 8, 2, 2, 512 | 16384, 4>(c, s);
-          case 96: return launch_t<KS, 1, 16, 3, 1, 512 | 16384, 4>(c, s);
+          case 128: return launch_t<KS, 2, 8, 2, 2, 512 | 16384 | FV, 4>(c, s);
+          case 96: return launch_t<KS, 1, 16, 3, 1, 512 | 16384 | FV, 4>(c, s);
         }
       }
 #endif
 #ifdef ISLPOSE_DEV
-      const bool m16 = c.bco == 128 && x3_m16(c);
-      if (m16) {
-        if (c.vin) return launch_t<KS, 2, 8, 2, 2, 512 | 32768 | 131072, 4>(c, s);
-        return launch_t<KS, 2, 8, 2, 2, 512 | 131072, 4>(c, s);
+      const bool m16 = FV == 0 && c.bco == 128 && x3_m16(c);   // (three-term only)
+      if constexpr (FV == 0) if (m16) {
+        if (c.vin) return launch_t<KS, 2, 8, 2, 2, 512 | 32768 | 131072 | FV, 4>(c, s);
+        return launch_t<KS, 2, 8, 2, 2, 512 | 131072 | FV, 4>(c, s);
       }
 #endif
       if (c.vin) {
-        if (c.bco == 128) return launch_t<KS, 2, 8, 2, 2, 512 | 32768, 4>(c, s);
+        if (c.bco == 128) return launch_t<KS, 2, 8, 2, 2, 512 | 32768 | FV, 4>(c, s);
         set_error("conv_x3: pooled-input staging without a variant (x3_vin_ok)");
         return hipErrorInvalidValue;
       }
       switch (c.bco) {
-        case 128: return launch_t<KS, 2, 8, 2, 2, 512, 4>(c, s);
-        case 96: return launch_t<KS, 1, 16, 3, 1, 512, 4>(c, s);
-        case 64: return launch_t<KS, 2, 8, 1, 2, 512, 4>(c, s);
-        case 32: return launch_t<KS, 1, 16, 1, 1, 512, 4>(c, s);
+        case 128: return launch_t<KS, 2, 8, 2, 2, 512 | FV, 4>(c, s);
+        case 96: return launch_t<KS, 1, 16, 3, 1, 512 | FV, 4>(c, s);
+        case 64: return launch_t<KS, 2, 8, 1, 2, 512 | FV, 4>(c, s);
+        case 32: return launch_t<KS, 1, 16, 1, 1, 512 | FV, 4>(c, s);
       }
     }
   }
   if constexpr (KS == 1) {
-    if (c.bco == 256 && x3_big_tiles(c)) return launch_t<KS, 4, 4, 2, 2, 4096, 1>(c, s);
+    if (c.bco == 256 && x3_big_tiles(c)) return launch_t<KS, 4, 4, 2, 2, 4096 | FV, 1>(c, s);
   }
   if constexpr (KS <= 3) {
     if (x3_big_tiles(c)) {
       if constexpr (KS == 3) {
         if (c.vin) {
-          if (c.bco == 128) return launch_t<KS, 2, 8, 2, 2, 32768, 4>(c, s);
-          if (x3_half64(c)) return launch_t<KS, 1, 8, 2, 1, 32768, 2>(c, s);
+          if (c.bco == 128) return launch_t<KS, 2, 8, 2, 2, 32768 | FV, 4>(c, s);
+          if (x3_half64(c)) return launch_t<KS, 1, 8, 2, 1, 32768 | FV, 2>(c, s);
         }
       }
       if (c.vin) {
         set_error("conv_x3: pooled-input staging without a variant (x3_vin_ok)");
         return hipErrorInvalidValue;
       }
-      if (x3_half64(c)) return launch_t<KS, 1, 8, 2, 1, 0, 2>(c, s);   // 8 waves of 64co x 32px, 256 px
+      if (x3_half64(c)) return launch_t<KS, 1, 8, 2, 1, FV, 2>(c, s);   // 8 waves of 64co x 32px, 256 px
       switch (c.bco) {
-        case 128: return launch_t<KS, 2, 8, 2, 2, 0, 4>(c, s);   // 16 waves, 64co x 64px each
-        case 96: return launch_t<KS, 1, 16, 3, 1, 0, 4>(c, s);   // 16 waves, 96co x 32px
-        case 64: return launch_t<KS, 2, 8, 1, 2, 0, 4>(c, s);    // 16 waves, 32co x 64px
-        case 32: return launch_t<KS, 1, 16, 1, 1, 0, 4>(c, s);   // 16 waves, 32co x 32px
+        case 128: return launch_t<KS, 2, 8, 2, 2, FV, 4>(c, s);   // 16 waves, 64co x 64px each
+        case 96: return launch_t<KS, 1, 16, 3, 1, FV, 4>(c, s);   // 16 waves, 96co x 32px
+        case 64: return launch_t<KS, 2, 8, 1, 2, FV, 4>(c, s);    // 16 waves, 32co x 64px
+        case 32: return launch_t<KS, 1, 16, 1, 1, FV, 4>(c, s);   // 16 waves, 32co x 32px
       }
     }
   }
@@ -2278,13 +2342,13 @@ static hipError_t launch_ks(const ConvLaunch& c, hipStream_t s) {
     // slabs; 8 waves measured 2-6 % over 4 waves of 64co x 64px / x 128px)
     if (c.ksplit <= 1 && c.bco == 128) {
       if (x3_small7(c)) {   // 64co x 64px blocks (=2: the steps' operands two steps ahead)
-        if (x3_small7_96(c)) return launch_t<KS, 2, 3, 1, 1, 256 | 128, 1>(c, s);
-        if (x3_small7_deep(c)) return launch_t<KS, 2, 2, 1, 1, 256 | 128, 1>(c, s);
-        return launch_t<KS, 2, 2, 1, 1, 256, 4>(c, s);
+        if (x3_small7_96(c)) return launch_t<KS, 2, 3, 1, 1, 256 | 128 | FV, 1>(c, s);
+        if (x3_small7_deep(c)) return launch_t<KS, 2, 2, 1, 1, 256 | 128 | FV, 1>(c, s);
+        return launch_t<KS, 2, 2, 1, 1, 256 | FV, 4>(c, s);
       }
-      if (x3_wide7_384(c)) return launch_t<KS, 2, 6, 2, 2, 65536, 1>(c, s);   // 12 waves, 384 px
-      if (x3_wide7(c)) return launch_t<KS, 2, 4, 2, 2, 0, 1>(c, s);
-      return launch_t<KS, 2, 4, 2, 1, 0, 1>(c, s);
+      if (x3_wide7_384(c)) return launch_t<KS, 2, 6, 2, 2, 65536 | FV, 1>(c, s);   // 12 waves, 384 px
+      if (x3_wide7(c)) return launch_t<KS, 2, 4, 2, 2, FV, 1>(c, s);
+      return launch_t<KS, 2, 4, 2, 1, FV, 1>(c, s);
     }
   }
   const bool ranged = c.ksplit > 1 && !c.ws;      // launch_conv_x3: in-block ranges
@@ -2303,13 +2367,13 @@ static hipError_t launch_ks(const ConvLaunch& c, hipStream_t s) {
         if (c.fold) {   // consumers of folded split-K partials (x3_fold_ok)
           switch (c.bco) {
             case 128:
-              if (split) return launch_t<KS, 2, 4, 2, 1, 2048 | 8192, 2>(c, s);
-              if (ranged) return launch_t<KS, 2, 4, 2, 1, 1024 | 8192, 2>(c, s);
-              return launch_t<KS, 2, 4, 2, 1, 8192, 2>(c, s);
+              if (split) return launch_t<KS, 2, 4, 2, 1, 2048 | 8192 | FV, 2>(c, s);
+              if (ranged) return launch_t<KS, 2, 4, 2, 1, 1024 | 8192 | FV, 2>(c, s);
+              return launch_t<KS, 2, 4, 2, 1, 8192 | FV, 2>(c, s);
             case 96:
-              if (split) return launch_t<KS, 3, 4, 1, 1, 2048 | 8192, 2>(c, s);
-              if (ranged) return launch_t<KS, 3, 4, 1, 1, 1024 | 8192, 2>(c, s);
-              return launch_t<KS, 3, 4, 1, 1, 8192, 2>(c, s);
+              if (split) return launch_t<KS, 3, 4, 1, 1, 2048 | 8192 | FV, 2>(c, s);
+              if (ranged) return launch_t<KS, 3, 4, 1, 1, 1024 | 8192 | FV, 2>(c, s);
+              return launch_t<KS, 3, 4, 1, 1, 8192 | FV, 2>(c, s);
           }
           set_error("conv_x3: fold without a variant (x3_fold_ok)");
           return hipErrorInvalidValue;
@@ -2322,22 +2386,22 @@ static hipError_t launch_ks(const ConvLaunch& c, hipStream_t s) {
       }
 #endif
       if constexpr (KS <= 3) {
-        if (x3_g2(c)) return launch_t<KS, 2, 4, 2, 1, 1024 | 32, 1>(c, s);   // two K groups of 8 waves
+        if (x3_g2(c)) return launch_t<KS, 2, 4, 2, 1, 1024 | 32 | FV, 1>(c, s);   // two K groups of 8 waves
       }
       if constexpr (KS <= 3) {
-        if (!split && !ranged && x3_halfsmall(c)) return launch_t<KS, 1, 4, 2, 1, 256, 4>(c, s);
+        if (!split && !ranged && x3_halfsmall(c)) return launch_t<KS, 1, 4, 2, 1, 256 | FV, 4>(c, s);
       }
       if constexpr (KS <= 3) {
         if (x3_deep(c)) {   // prefetch two K steps ahead
           switch (c.bco) {
             case 128:
-              if (split) return launch_t<KS, 2, 4, 2, 1, 2048 | 128, 1>(c, s);
-              if (ranged) return launch_t<KS, 2, 4, 2, 1, 1024 | 128, 1>(c, s);
-              return launch_t<KS, 2, 4, 2, 1, 128, 1>(c, s);
+              if (split) return launch_t<KS, 2, 4, 2, 1, 2048 | 128 | FV, 1>(c, s);
+              if (ranged) return launch_t<KS, 2, 4, 2, 1, 1024 | 128 | FV, 1>(c, s);
+              return launch_t<KS, 2, 4, 2, 1, 128 | FV, 1>(c, s);
             case 96:
-              if (split) return launch_t<KS, 3, 4, 1, 1, 2048 | 128, 1>(c, s);
-              if (ranged) return launch_t<KS, 3, 4, 1, 1, 1024 | 128, 1>(c, s);
-              return launch_t<KS, 3, 4, 1, 1, 128, 1>(c, s);
+              if (split) return launch_t<KS, 3, 4, 1, 1, 2048 | 128 | FV, 1>(c, s);
+              if (ranged) return launch_t<KS, 3, 4, 1, 1, 1024 | 128 | FV, 1>(c, s);
+              return launch_t<KS, 3, 4, 1, 1, 128 | FV, 1>(c, s);
           }
         }
       }
@@ -2346,47 +2410,47 @@ static hipError_t launch_ks(const ConvLaunch& c, hipStream_t s) {
         if (x3_pps2(c)) {   // two chunk pairs per K step: twice the MFMAs between barriers
           switch (c.bco) {
             case 128:
-              if (split) return launch_t<KS, 2, 4, 2, 1, 2048 | 4096, 2>(c, s);
-              if (ranged) return launch_t<KS, 2, 4, 2, 1, 1024 | 4096, 2>(c, s);
-              return launch_t<KS, 2, 4, 2, 1, 4096, 2>(c, s);
+              if (split) return launch_t<KS, 2, 4, 2, 1, 2048 | 4096 | FV, 2>(c, s);
+              if (ranged) return launch_t<KS, 2, 4, 2, 1, 1024 | 4096 | FV, 2>(c, s);
+              return launch_t<KS, 2, 4, 2, 1, 4096 | FV, 2>(c, s);
             case 96:
-              if (split) return launch_t<KS, 3, 4, 1, 1, 2048 | 4096, 2>(c, s);
-              if (ranged) return launch_t<KS, 3, 4, 1, 1, 1024 | 4096, 2>(c, s);
-              return launch_t<KS, 3, 4, 1, 1, 4096, 2>(c, s);
+              if (split) return launch_t<KS, 3, 4, 1, 1, 2048 | 4096 | FV, 2>(c, s);
+              if (ranged) return launch_t<KS, 3, 4, 1, 1, 1024 | 4096 | FV, 2>(c, s);
+              return launch_t<KS, 3, 4, 1, 1, 4096 | FV, 2>(c, s);
           }
         }
       }
 #endif
       if (c.bco == 128 && x3_halfco(c)) {   // two blocks of 4 waves (64co x 32px) per 128-channel tile
         if constexpr (KS == 7) {
-          if (split && x3_small7_deep(c)) return launch_t<KS, 2, 2, 1, 1, 2048 | 256 | 128, 1>(c, s);
+          if (split && x3_small7_deep(c)) return launch_t<KS, 2, 2, 1, 1, 2048 | 256 | 128 | FV, 1>(c, s);
         }
-        if (split && x3_px64_mode() >= 2) return launch_t<KS, 2, 2, 1, 1, 2048 | 256, 4>(c, s);
-        if (split) return launch_t<KS, 1, 4, 2, 1, 2048 | 256, 4>(c, s);
+        if (split && x3_px64_mode() >= 2) return launch_t<KS, 2, 2, 1, 1, 2048 | 256 | FV, 4>(c, s);
+        if (split) return launch_t<KS, 1, 4, 2, 1, 2048 | 256 | FV, 4>(c, s);
 #ifdef ISLPOSE_DEV
-        if (ranged) return launch_t<KS, 1, 4, 2, 1, 1024 | 256, 4>(c, s);
+        if (ranged) return launch_t<KS, 1, 4, 2, 1, 1024 | 256 | FV, 4>(c, s);
 #endif
-        if (!ranged) return launch_t<KS, 1, 4, 2, 1, 256, 4>(c, s);
+        if (!ranged) return launch_t<KS, 1, 4, 2, 1, 256 | FV, 4>(c, s);
       }
       switch (c.bco) {
         case 128:   // 8 waves of 64co x 32px
-          if (split) return launch_t<KS, 2, 4, 2, 1, 2048, 2>(c, s);
-          if (ranged) return launch_t<KS, 2, 4, 2, 1, 1024, 2>(c, s);
-          return launch_t<KS, 2, 4, 2, 1, 0, 2>(c, s);
+          if (split) return launch_t<KS, 2, 4, 2, 1, 2048 | FV, 2>(c, s);
+          if (ranged) return launch_t<KS, 2, 4, 2, 1, 1024 | FV, 2>(c, s);
+          return launch_t<KS, 2, 4, 2, 1, FV, 2>(c, s);
         case 96:    // 12 waves of 32co x 32px (6 on 64-pixel tiles: x3_px64)
-          if (split && x3_px64(c)) return launch_t<KS, 3, 2, 1, 1, 2048, 4>(c, s);
-          if (split) return launch_t<KS, 3, 4, 1, 1, 2048, 2>(c, s);
-          if (ranged) return launch_t<KS, 3, 4, 1, 1, 1024, 2>(c, s);
-          return launch_t<KS, 3, 4, 1, 1, 0, 2>(c, s);
+          if (split && x3_px64(c)) return launch_t<KS, 3, 2, 1, 1, 2048 | FV, 4>(c, s);
+          if (split) return launch_t<KS, 3, 4, 1, 1, 2048 | FV, 2>(c, s);
+          if (ranged) return launch_t<KS, 3, 4, 1, 1, 1024 | FV, 2>(c, s);
+          return launch_t<KS, 3, 4, 1, 1, FV, 2>(c, s);
       }
     }
   }
   switch (c.bco) {
 #define X3_CASE(BC, WMS, WNS, WMM, WNN)                                           \
   case BC:                                                                        \
-    if (split) return launch_t<KS, WMS, WNS, WMM, WNN, 2048, 2>(c, s);            \
-    if (ranged) return launch_t<KS, WMS, WNS, WMM, WNN, 1024, 2>(c, s);           \
-    return launch_t<KS, WMS, WNS, WMM, WNN, 0, 2>(c, s);
+    if (split) return launch_t<KS, WMS, WNS, WMM, WNN, 2048 | FV, 2>(c, s);            \
+    if (ranged) return launch_t<KS, WMS, WNS, WMM, WNN, 1024 | FV, 2>(c, s);           \
+    return launch_t<KS, WMS, WNS, WMM, WNN, FV, 2>(c, s);
     X3_CASE(128, 2, 2, 2, 2)
     X3_CASE(96, 1, 4, 3, 1)
     X3_CASE(64, 1, 4, 2, 1)
@@ -2416,7 +2480,7 @@ double conv_x3_mfma_flops(const ConvLaunch& c) {
   const int BPX = x3_big_tiles(c) ? x3_big_bpx(c) : x3_wide7_384(c) ? 384 : x3_wide7(c) ? 256 : 128;
   const double co = (double)((c.cout + c.bco - 1) / c.bco) * c.bco;
   const double px = std::ceil((double)c.H * c.W / tile_pixels(c, BPX, x3_segmax(BPX))) * BPX;
-  return 3.0 * 2.0 * co * (((c.cin_chunks + 1) / 2) * 16.0) * c.ks * c.ks * px * c.n;
+  return x3_products(c) * 2.0 * co * (((c.cin_chunks + 1) / 2) * 16.0) * c.ks * c.ks * px * c.n;
 }
 
 int x3_split_ranges(const ConvLaunch& c, bool* across_blocks) {
@@ -2526,8 +2590,9 @@ static hipError_t launch_wr_t(const ConvLaunch& c, int S, hipStream_t s) {
   const long long nb = (long long)c.n * a.px_tiles * a.co_tiles;
   if (nb <= 0 || nb > 0x7fffffff) { set_error("conv_x3_wr: bad grid"); return hipErrorInvalidValue; }
   a.nblocks = (int)nb;
-  t_last_variant = x3_variant_code(8 | (S > 1 ? 1024 : 0), KS, 32 * WN, 32);
-  hipLaunchKernelGGL((conv_x3_wr<KS, WN, DEPTH>), dim3(a.nblocks), dim3(64 * S), 0, s, a);
+  t_last_variant = x3_variant_code(8 | (S > 1 ? 1024 : 0) | (c.f16 ? X3V_F16 : 0), KS, 32 * WN, 32);
+  if (c.f16) hipLaunchKernelGGL((conv_x3_wr<KS, WN, DEPTH, true>), dim3(a.nblocks), dim3(64 * S), 0, s, a);
+  else hipLaunchKernelGGL((conv_x3_wr<KS, WN, DEPTH, false>), dim3(a.nblocks), dim3(64 * S), 0, s, a);
   return hipGetLastError();
 }
 
@@ -2544,6 +2609,10 @@ static hipError_t launch_x3_wr(const ConvLaunch& c, int S, hipStream_t s) {
 }
 
 hipError_t launch_conv_x3(const ConvLaunch& c0, hipStream_t s) {
+  if (c0.cout7 > 0 && c0.f16) {
+    set_error("conv_x3: the fused 1x1 pair has no one-term form (the plan runs it unfused)");
+    return hipErrorInvalidValue;
+  }
   if (c0.cout7 > 0) return launch_x3_fused67(c0, s);
   ConvLaunch c = c0;
   const X3Ranges r = x3_ranges(c);
@@ -2567,9 +2636,9 @@ hipError_t launch_conv_x3(const ConvLaunch& c0, hipStream_t s) {
     c.ws = nullptr;        // in-block ranges (or none)
   }
   switch (c.ks) {
-    case 1: return launch_ks<1>(c, s);
-    case 3: return launch_ks<3>(c, s);
-    case 7: return launch_ks<7>(c, s);
+    case 1: return c.f16 ? launch_ks<1, X3V_F16>(c, s) : launch_ks<1, 0>(c, s);
+    case 3: return c.f16 ? launch_ks<3, X3V_F16>(c, s) : launch_ks<3, 0>(c, s);
+    case 7: return c.f16 ? launch_ks<7, X3V_F16>(c, s) : launch_ks<7, 0>(c, s);
   }
   set_error("conv_x3: unsupported kernel size");
   return hipErrorInvalidValue;

@@ -54,6 +54,10 @@ struct ConvLaunch {
   const void* wx3 = nullptr;   // pre-split weights [co_tile][pair][ky][kx][hi|lo][h][BCO][8] fp16
   float wscale_inv = 1.f;      // 2^-s, the inverse of the per-layer weight scale
   int* range_flag = nullptr;   // raised when an output leaves the fp16 split range
+  // ISL_PREC_FP16: one fp16 product per MAC.  wx3 then holds the hi halves alone -- the same
+  // layouts without their [hi|lo] dimension (runtime.cpp pack_hi_only) -- and the kernels
+  // round the activations to fp16 once at staging; launch_conv_x3, launch_conv_x3_rgb only
+  int f16 = 0;
   // split-K workspace (conv_x3 on grids too small to fill the GPU); null = no split
   float* ws = nullptr;
   size_t ws_floats = 0;
@@ -137,6 +141,7 @@ constexpr int X3V_RGB = 1 << 18;
 constexpr int X3V_FOLD_OUT = 1 << 19;   // a split-K producer whose reduce was folded into its consumers
 constexpr int X3V_C12 = 4;              // conv1_1 -> conv1_2 -> pair-max in one launch (conv_c12.hip)
 constexpr int X3V_W2 = 64;              // split-fp16 Winograd F(2x2, 3x3) (wino_f16.hip)
+constexpr int X3V_F16 = 2;              // one-term fp16 products (ISL_PREC_FP16; a template VAR bit too)
 
 constexpr int x3_variant_code(int var, int ks, int bpx, int bco) {
   return (var & 0xfffff) | ((bpx / 32) << 20) | ((bco / 32) << 25) | ((ks / 2) << 29);

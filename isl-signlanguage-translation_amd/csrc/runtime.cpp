@@ -79,6 +79,11 @@ struct ConvLayer {
   // through that channel map (d_wx3p)
   void* d_wx3p = nullptr;
   float *d_bp = nullptr, *d_sp = nullptr;
+  // ISL_PREC_FP16: the hi halves alone of d_wx3 / d_wx3w / d_wrgb (pack_hi_only: the same 2^s,
+  // the same layouts without [hi|lo]), built when the mode is first used (upload_hi_packs)
+  void* d_hx3 = nullptr;
+  void* d_hx3w = nullptr;
+  void* d_hrgb = nullptr;
 };
 
 static ConvLayer mk(const std::string& name, int cin, int cout, int k, int act, const std::string& prelu = "") {
@@ -215,6 +220,7 @@ struct isl_net {
   OutRef out0{}, out1{};
   int n_out = 2;
   bool packed = false;
+  bool packed_hi = false;      // the hi-only packs (ISL_PREC_FP16) match the current weights
   // plan
   int pn = 0, ph = 0, pw = 0;
   std::vector<Act> act;
@@ -285,6 +291,9 @@ struct isl_net {
   hipStream_t cap_stream = nullptr;
   // conv algorithm (ISL_ALGO_*) and the split-fp16 range flag (isl_net_check)
   int algo = ISL_ALGO_X3;
+  // ISL_PREC_*: products per MAC of the ISL_ALGO_X3 convs (isl_net_set_precision, env
+  // ISLPOSE_PRECISION=fp32|fp16); stored without effect under the other algorithms
+  int precision = ISL_PREC_FP32;
   int split_k = 1;             // isl_net_set_split_k: K-range mode (env ISLPOSE_X3_SPLITK=0|1|2)
   int* d_flag = nullptr;
   // range-guard trips: seen by the synchronous check (host count) and by the stream-ordered
@@ -804,10 +813,47 @@ static std::vector<_Float16> pack_wino_x3(const ConvLayer& c, float* inv_scale) 
 }
 #endif
 
+// The hi halves of a split pack whose [hi|lo] dimension has `group` fp16 values per plane
+// (pack_x3: 2 * bco * 8, pack_x3_rgb: 2 * 64 * 8): the planes [.. ][hi] in order, i.e. the same
+// layout without that dimension and the same 2^s -- the filters rounded once to fp16 (RNE)
+static std::vector<_Float16> pack_hi_only(const std::vector<_Float16>& split, size_t group) {
+  std::vector<_Float16> out(split.size() / 2);
+  for (size_t g = 0; g < out.size() / group; ++g)
+    std::copy(split.begin() + 2 * g * group, split.begin() + (2 * g + 1) * group, out.begin() + g * group);
+  return out;
+}
+
 static void drop_all_graphs(isl_net* net);
+
+// ISL_PREC_FP16's filters: built when a run first needs them after a weight upload (at the
+// upload itself when the mode is already selected), kept across precision switches
+static int upload_hi_packs(isl_net* net) {
+  for (ConvLayer& c : net->layers) {
+    float inv = 1.f;
+    {
+      std::vector<_Float16> hp = pack_hi_only(pack_x3(c, c.bco, &inv), (size_t)2 * c.bco * 8);
+      if (inv != c.x3_inv) return fail(ISL_E_STATE, "hi-only pack: scale mismatch");
+      if (!c.d_hx3) HIP_OK(hipMalloc(&c.d_hx3, hp.size() * sizeof(_Float16)));
+      HIP_OK(hipMemcpy(c.d_hx3, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    }
+    if (rgb_layer(c)) {
+      std::vector<_Float16> hp = pack_hi_only(pack_x3_rgb(c), (size_t)2 * 64 * 8);
+      if (!c.d_hrgb) HIP_OK(hipMalloc(&c.d_hrgb, hp.size() * sizeof(_Float16)));
+      HIP_OK(hipMemcpy(c.d_hrgb, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    }
+    if (c.x3_wide) {
+      std::vector<_Float16> hp = pack_hi_only(pack_x3(c, 256, &inv), (size_t)2 * 256 * 8);
+      if (!c.d_hx3w) HIP_OK(hipMalloc(&c.d_hx3w, hp.size() * sizeof(_Float16)));
+      HIP_OK(hipMemcpy(c.d_hx3w, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    }
+  }
+  net->packed_hi = true;
+  return ISL_OK;
+}
 
 static int upload_params(isl_net* net) {
   drop_all_graphs(net);   // new weight scales: the captured launches' arguments are stale
+  net->packed_hi = false; // both packs follow the weights
   for (ConvLayer& c : net->layers) {
     if (!c.has_w || !c.has_b || (c.act == ACT_PRELU && !c.has_s))
       return fail(ISL_E_STATE, "parameter missing for layer " + c.name);
@@ -1059,6 +1105,13 @@ static int default_algo() {
   return ISL_ALGO_X3;
 }
 
+// Precision of a net's ISL_ALGO_X3 convs (isl_net_set_precision); ISLPOSE_PRECISION=fp32|fp16
+// sets the default at isl_net_create (unset or anything else: fp32).
+static int default_precision() {
+  const char* e = getenv("ISLPOSE_PRECISION");
+  return e && std::string(e) == "fp16" ? ISL_PREC_FP16 : ISL_PREC_FP32;
+}
+
 #ifdef ISLPOSE_DEV
 // ISL_ALGO_X3 runs 3x3 layers on the direct split-fp16 kernel; ISLPOSE_X3_WINO=1
 // selects the split-fp16 Winograd kernel instead.  It is fp32-accurate (rel err
@@ -1304,7 +1357,12 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
   bool fused = false;   // the previous conv wrote the pair-max buffer of this pool
   int vin_buf = -1;     // this conv stages from that buffer (the pool op was skipped)
   const bool fuse_pools = fused_pool_enabled(), pool_input = fuse_pools && pool_input_enabled();
-  const int f67 = net->algo == ISL_ALGO_X3 ? fuse67_mode() : 0;
+  // ISL_PREC_FP16 (ISL_ALGO_X3 only): every x3 conv on the one-term form of the variant the fp32
+  // plan picks, from the hi-only packs.  The fused launches (the 1x1 pair, conv1_1 -> conv1_2)
+  // have no one-term form and run as their layers; the Winograd kernel is never chosen.
+  const bool h16 = net->algo == ISL_ALGO_X3 && net->precision == ISL_PREC_FP16;
+  if (h16 && !net->packed_hi) return fail(ISL_E_STATE, "fp16 precision: hi-only filters not uploaded");
+  const int f67 = net->algo == ISL_ALGO_X3 && !h16 ? fuse67_mode() : 0;
   size_t perm_op = (size_t)-1;   // the pair (perm_op, perm_op + 1) runs as its permuted two launches
   for (size_t k = 0; k < net->ops.size(); ++k) {
     const Op& op = net->ops[k];
@@ -1345,7 +1403,7 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
     // conv1_1 (rgb kernel) -> conv1_2 -> pool: both convs and the pool in one launch writing the
     // pooled map (or, ISLPOSE_C12=2, the pool's pair-max buffer), where conv1_1's output feeds
     // conv1_2 only (conv_c12.hip)
-    const int c12m = c12_mode();
+    const int c12m = h16 ? 0 : c12_mode();
     if (net->algo == ISL_ALGO_X3 && op.type == 0 && vin_buf < 0 && fuse_pools && c12m &&
         k + 2 < net->ops.size() && net->layers[op.layer].d_wrgb && rgb_kernel_enabled()) {
       const Op& o2 = net->ops[k + 1];
@@ -1463,6 +1521,10 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
         Lw.bco = 256;
         if (x3_wide1(Lw)) { L.bco = 256; L.wx3 = c.d_wx3w; }
       }
+      if (h16) {   // (perm is never set: the pair is not fused in this mode)
+        L.f16 = 1;
+        L.wx3 = L.bco == 256 && c.x3_wide ? c.d_hx3w : c.d_hx3;
+      }
       // the next op pools this conv's output: write pair maxima to its half-width buffer
       if (k + 1 < net->ops.size() && net->ops[k + 1].type == 1 && net->ops[k + 1].in == op.out && op.out_coff == 0 &&
           net->ops[k + 1].C == c.cout && fuse_pools && x3_hpool_ok(L)) {
@@ -1476,7 +1538,7 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
       // no fold, no K ranges
       const bool pool_side = (k > 0 && net->ops[k - 1].type == 1 && net->ops[k - 1].out == op.in) ||
                              (k + 1 < net->ops.size() && net->ops[k + 1].type == 1 && net->ops[k + 1].in == op.out);
-      if (!perm && !pool_side && w2_enabled(L) && c.d_ww && !L.vin && !L.hpool && far.fold_ws_off[k] < 0 &&
+      if (!h16 && !perm && !pool_side && w2_enabled(L) && c.d_ww && !L.vin && !L.hpool && far.fold_ws_off[k] < 0 &&
           far.fold_tab_off[k] < 0 && x3_split_ranges(L, nullptr) <= 1) {
         ConvLaunch Lw = L;
         Lw.wx3 = c.d_ww;
@@ -1519,7 +1581,7 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
         L.fold = far.fold_tab + far.fold_tab_off[k];
       }
       if (c.d_wrgb && x3_rgb_fits(L) && rgb_kernel_enabled() && !L.vin) {
-        L.wx3 = c.d_wrgb;
+        L.wx3 = h16 ? c.d_hrgb : c.d_wrgb;
         HIP_OK(launch_conv_x3_rgb(L, s));
         kind = 3; mf = conv_x3_rgb_mfma_flops(L);
       } else {
@@ -1569,7 +1631,7 @@ static unsigned long long run_key(const isl_net* net) {
   unsigned long long h = 1469598103934665603ull;
   auto mix = [&](unsigned long long v) { h = (h ^ v) * 1099511628211ull; };
   mix((unsigned long long)net->pn);
-  mix((unsigned long long)net->split_k + 16 * (unsigned long long)net->algo);
+  mix((unsigned long long)net->split_k + 16 * (unsigned long long)net->algo + 256 * (unsigned long long)net->precision);
   for (const char* name : kRunKeySwitches) {
     const char* v = getenv(name);
     for (const char* c = name; *c; ++c) mix((unsigned char)*c);
@@ -1756,6 +1818,7 @@ int isl_net_create(int kind, int device, isl_net** out) {
   net->kind = kind;
   net->device = device;
   net->algo = default_algo();
+  net->precision = default_precision();
   {
     // K-range mode (isl_net_set_split_k): 1 canonical ranges (default), 0 none, 2 latency
     const char* e = getenv("ISLPOSE_X3_SPLITK");
@@ -1793,6 +1856,9 @@ int isl_net_destroy(isl_net* net) {
     if (c.d_wx3f) (void)hipFree(c.d_wx3f);
     if (c.d_wx3f7) (void)hipFree(c.d_wx3f7);
     if (c.d_wx3p) (void)hipFree(c.d_wx3p);
+    if (c.d_hx3) (void)hipFree(c.d_hx3);
+    if (c.d_hx3w) (void)hipFree(c.d_hx3w);
+    if (c.d_hrgb) (void)hipFree(c.d_hrgb);
     if (c.d_bp) (void)hipFree(c.d_bp);
     if (c.d_sp) (void)hipFree(c.d_sp);
   }
@@ -1876,7 +1942,11 @@ int isl_net_set_param(isl_net* net, const char* caffe_name, const float* host, i
 
 static int prepare(isl_net* net) {
   HIP_OK(hipSetDevice(net->device));
-  if (!net->packed) return upload_params(net);
+  if (!net->packed) {
+    const int rc = upload_params(net);
+    if (rc) return rc;
+  }
+  if (net->precision == ISL_PREC_FP16 && net->algo == ISL_ALGO_X3 && !net->packed_hi) return upload_hi_packs(net);
   return ISL_OK;
 }
 
@@ -2049,6 +2119,16 @@ int isl_net_set_algo(isl_net* net, int algo) {
 }
 
 int isl_net_get_algo(const isl_net* net) { return net ? net->algo : fail(ISL_E_ARG, "net is NULL"); }
+
+int isl_net_set_precision(isl_net* net, int precision) {
+  if (!net) return fail(ISL_E_ARG, "net is NULL");
+  if (precision != ISL_PREC_FP32 && precision != ISL_PREC_FP16) return fail(ISL_E_ARG, "unknown precision");
+  // (captured graphs are keyed by the precision, run_key: a switch re-keys them)
+  net->precision = precision;
+  return ISL_OK;
+}
+
+int isl_net_get_precision(const isl_net* net) { return net ? net->precision : fail(ISL_E_ARG, "net is NULL"); }
 
 int isl_lane_stream_create(int device, int priority_class, void** stream) {
   if (!stream) return fail(ISL_E_ARG, "stream is NULL");

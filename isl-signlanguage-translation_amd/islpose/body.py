@@ -48,7 +48,10 @@ class FrameResult:
 
 class BodyEstimator:
     def __init__(self, weights: dict = None, model_type: str = "body25", device: int = 0, scale_search=(0.5,),
-                 caps=None, net: "rt.Net" = None):
+                 caps=None, net: "rt.Net" = None, precision: str = None):
+        """precision: 'fp32' or 'fp16' (rt.Net.set_precision) for the net, or None to keep
+        the net's own -- fp32 unless ISLPOSE_PRECISION=fp16 was set when it was created."""
+        rt.check_precision(precision)
         self.kind = KINDS[model_type]
         self.model_type = model_type
         self.device = device
@@ -58,6 +61,8 @@ class BodyEstimator:
             net = rt.Net(self.kind, device)
             net.load_weights(weights)
         assert net.kind == self.kind
+        if precision is not None:
+            net.set_precision(precision)
         self.net = net
         self.njoint, self.npaf = NJOINT[self.kind], NPAF[self.kind]
 

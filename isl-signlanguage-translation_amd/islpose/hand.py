@@ -23,13 +23,19 @@ CROP_CHUNK = 64     # hand crops per batched pass of estimate_crops
 
 
 class HandEstimator:
-    def __init__(self, weights: dict = None, device: int = 0, scale_search=HAND_SCALES, net: "rt.Net" = None):
+    def __init__(self, weights: dict = None, device: int = 0, scale_search=HAND_SCALES, net: "rt.Net" = None,
+                 precision: str = None):
+        """precision: 'fp32' or 'fp16' (rt.Net.set_precision) for the net, or None to keep
+        the net's own -- fp32 unless ISLPOSE_PRECISION=fp16 was set when it was created."""
+        rt.check_precision(precision)
         self.device = device
         self.scale_search = tuple(scale_search)
         if net is None:
             net = rt.Net(rt.ISL_HAND, device)
             net.load_weights(weights)
         assert net.kind == rt.ISL_HAND
+        if precision is not None:
+            net.set_precision(precision)
         self.net = net
 
     def run_scales(self, crops):

@@ -16,6 +16,17 @@ ISL_BODY25, ISL_COCO, ISL_HAND = 0, 1, 2
 # conv arithmetic (isl_algo): split-fp16 x3 (default), Winograd fp32, direct fp32
 ISL_ALGO_X3, ISL_ALGO_WINO, ISL_ALGO_DIRECT = 0, 1, 2
 ALGOS = {"x3": ISL_ALGO_X3, "wino": ISL_ALGO_WINO, "direct": ISL_ALGO_DIRECT}
+# precision of the x3 convs (isl_precision): fp32-accurate three-term products (default), or one
+# fp16 product per multiply-add (opt-in; ~2e-3 of the maps' maximum in error)
+ISL_PREC_FP32, ISL_PREC_FP16 = 0, 1
+PRECISIONS = {"fp32": ISL_PREC_FP32, "fp16": ISL_PREC_FP16}
+
+
+def check_precision(name):
+    """`name` if it is a key of PRECISIONS (or None: keep the net's own), else ValueError."""
+    if name is not None and name not in PRECISIONS:
+        raise ValueError("unknown precision %r (expected one of %s)" % (name, ", ".join(PRECISIONS)))
+    return name
 
 LIB_PATH = os.environ.get("ISLPOSE_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "libislpose.so"))
 
@@ -26,7 +37,8 @@ EXPORTS = ["isl_abi_version", "isl_last_error", "isl_net_create", "isl_net_destr
            "isl_net_set_algo", "isl_net_get_algo", "isl_net_check", "isl_net_preprocess_crops",
            "isl_sign_param_count", "isl_sign_classify", "isl_net_set_split_k", "isl_net_arena_info",
            "isl_debug_np_sum", "isl_hand_post_crops", "isl_net_check_async", "isl_net_range_info",
-           "isl_net_op_info", "isl_net_set_graph", "isl_lane_stream_create", "isl_lane_stream_destroy"]
+           "isl_net_op_info", "isl_net_set_graph", "isl_lane_stream_create", "isl_lane_stream_destroy",
+           "isl_net_set_precision", "isl_net_get_precision"]
 
 
 class IslCaps(ctypes.Structure):
@@ -81,6 +93,8 @@ def lib():
                                            ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.isl_net_set_algo.argtypes = [vp, i32]
     L.isl_net_get_algo.argtypes = [vp]
+    L.isl_net_set_precision.argtypes = [vp, i32]
+    L.isl_net_get_precision.argtypes = [vp]
     L.isl_net_check.argtypes = [vp, i32]
     L.isl_net_check_async.argtypes = [vp, vp, vp]
     L.isl_net_range_info.argtypes = [vp, ctypes.POINTER(i64)]
@@ -237,7 +251,7 @@ def ptr(t) -> ctypes.c_void_p:
 def decode_variant(code: int) -> dict:
     """isl_net_op_info's variant code -> dict(var=VAR bits, bpx, bco, ks, rgb, pool_fused, ...):
     wave_ranges (conv_x3_wr, VAR 8), c12 (conv1_1 -> conv1_2 in one launch, 4), wino2 (the
-    split-fp16 Winograd kernel wino_f16, 64)."""
+    split-fp16 Winograd kernel wino_f16, 64), f16 (one-term fp16 products, precision 'fp16', 2)."""
     if code == -1:
         return {"pool_fused": True}
     if code == -2:
@@ -251,7 +265,8 @@ def decode_variant(code: int) -> dict:
             "union": bool(code & 512), "ranged": bool(code & 1024), "split": bool(code & 2048),
             "pairs2": bool(code & 4096), "vin": bool(code & 32768), "sib": bool(code & 65536),
             "fold": bool(code & 8192), "m16": bool(code & 131072), "fold_out": bool(code & (1 << 19)),
-            "wave_ranges": bool(code & 8), "c12": bool(code & 4), "wino2": bool(code & 64)}
+            "wave_ranges": bool(code & 8), "c12": bool(code & 4), "wino2": bool(code & 64),
+            "f16": bool(code & 2)}
 
 
 class Net:
@@ -330,6 +345,33 @@ class Net:
         """'x3' (split-fp16 on the FP16 matrix cores, fp32-accurate; default), 'wino'
         (Winograd F(2x2,3x3), FP32 MFMA) or 'direct' (implicit GEMM, FP32 MFMA)."""
         check(lib().isl_net_set_algo(self.h, ALGOS[algo]), "isl_net_set_algo")
+
+    # -- precision of the x3 convs ---------------------------------------------------
+    @property
+    def precision(self) -> str:
+        p = lib().isl_net_get_precision(self.h)
+        return {v: k for k, v in PRECISIONS.items()}[p]
+
+    def set_precision(self, name: str):
+        """'fp32' (three fp16 products per multiply-add, fp32-accurate; default, or the env
+        ISLPOSE_PRECISION at creation) or 'fp16' (one product: a third of the matrix work, half
+        the operand bytes, ~2e-3 of the maps' maximum in error).  It changes the 'x3' algorithm
+        only; the range guard and its fp32 ('direct') recompute are unchanged.  Unknown names
+        raise ValueError."""
+        check(lib().isl_net_set_precision(self.h, PRECISIONS[check_precision(name)]), "isl_net_set_precision")
+
+    def precision_scope(self, name: str):
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            prev = self.precision
+            self.set_precision(name)
+            try:
+                yield
+            finally:
+                self.set_precision(prev)
+        return scope()
 
     def set_split_k(self, mode):
         """K-range mode of the x3 convs (isl_net_set_split_k): 1 canonical ranges (default,

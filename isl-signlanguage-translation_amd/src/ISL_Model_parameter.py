@@ -80,13 +80,13 @@ class ISLSignPos(object):
     def state_key(self):
         """Identity of what produces the keypoints: the two modules, their current
         parameters (storage and in-place version, as _NativeNet.native() tracks them)
-        and the native nets' split-K state."""
+        and the native nets' split-K state and precision (src.model set_precision)."""
         def part(m):
             if m is None:
                 return (None,)
             net = getattr(m, "_native_net", None)
             return (id(m), tuple((p.data_ptr(), p._version) for p in m.parameters()),
-                    getattr(net, "split_k", None))
+                    getattr(net, "split_k", None), getattr(m, "precision", None))
         return part(self.pt_body) + part(self.pt_hand)
 
     def bodypos(self, oriImg):

@@ -7,6 +7,11 @@ with identical dtypes, shapes and values.  The whole call runs on the GPU
 (pre-processing, network, resize, blur/NMS, PAF, assembly) -- on a host without a
 visible HIP device, on the CPU instead (islpose.cpu, as the reference); ``scale_search``
 defaults to the reference's [0.5] and can be changed per instance.
+``precision`` (keyword only, not in the reference) selects the arithmetic of the GPU
+convolutions: 'fp32', or 'fp16' (one fp16 product per multiply-add, faster, ~2e-3 of the maps'
+maximum in error); the default None is the library's own, fp32 unless ISLPOSE_PRECISION=fp16
+is set.  An unknown value raises ValueError.  The CPU path is fp32 whatever
+is given.
 ``estimate_batch(frames)`` processes a batch of frames in one pass.
 """
 from __future__ import annotations
@@ -15,6 +20,7 @@ import numpy as np
 import torch
 
 from islpose import cpu
+from islpose import runtime as rt
 from islpose.body import BodyEstimator
 
 from . import util
@@ -22,7 +28,8 @@ from .model import bodypose_25_model, bodypose_model
 
 
 class Body(object):
-    def __init__(self, model_path, model_type="coco"):
+    def __init__(self, model_path, model_type="coco", *, precision=None):
+        rt.check_precision(precision)
         if model_type == "coco":
             self.model, self.njoint, self.npaf = bodypose_model(), 19, 38
         elif model_type == "body25":
@@ -37,6 +44,8 @@ class Body(object):
                                                                             weights_only=True)
         self.model.load_state_dict(util.transfer(self.model, weights))
         self.model.eval()
+        self.precision = precision
+        self.model.set_precision(precision)
         self.scale_search = [0.5]          # body.py:41
         self._est = None
 

@@ -3,6 +3,9 @@
 Same constructor (hand.py:16-22) and call (hand.py:24-74): 4-scale pyramid,
 fp64 averaging, blur, connected components, largest-mass component, first
 maximum -- all on the GPU (on a host without a visible HIP device, on the CPU: islpose.cpu).  ``estimate_batch(crops)`` takes equal-size crops.
+``precision`` (keyword only, not in the reference): 'fp32' or 'fp16' for the GPU convolutions;
+the default None is the library's own (fp32 unless ISLPOSE_PRECISION=fp16 is set); an unknown
+value raises ValueError; no effect on the CPU path, which is fp32.
 """
 from __future__ import annotations
 
@@ -10,6 +13,7 @@ import numpy as np
 import torch
 
 from islpose import cpu
+from islpose import runtime as rt
 from islpose.hand import HandEstimator
 
 from . import util
@@ -17,7 +21,8 @@ from .model import handpose_model
 
 
 class Hand(object):
-    def __init__(self, model_path):
+    def __init__(self, model_path, *, precision=None):
+        rt.check_precision(precision)
         self.model = handpose_model()
         if torch.cuda.is_available():
             self.model = self.model.cuda()
@@ -25,6 +30,8 @@ class Hand(object):
                                                                             weights_only=True)
         self.model.load_state_dict(util.transfer(self.model, weights))
         self.model.eval()
+        self.precision = precision
+        self.model.set_precision(precision)
         self._est = None
 
     def estimator(self) -> HandEstimator:

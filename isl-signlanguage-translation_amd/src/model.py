@@ -54,6 +54,22 @@ class _NativeNet(nn.Module):
         super().__init__()
         object.__setattr__(self, "_native_net", None)
         object.__setattr__(self, "_native_key", None)
+        object.__setattr__(self, "_native_precision", None)
+
+    def set_precision(self, name):
+        """Precision of this module's native net (rt.Net.set_precision): 'fp32', 'fp16', or None
+        for the library default (fp32 unless ISLPOSE_PRECISION=fp16).  Kept on the module, so the
+        net created later -- and everything built on the module, ISLSignPos included -- carries
+        it.  On a host without a HIP device the CPU forward stays fp32 whatever is set."""
+        rt.check_precision(name)
+        object.__setattr__(self, "_native_precision", name)
+        if name is not None and self._native_net is not None:
+            self._native_net.set_precision(name)
+
+    @property
+    def precision(self):
+        """The native net's precision once it exists, else what set_precision stored."""
+        return self._native_net.precision if self._native_net is not None else self._native_precision
 
     def _param_key(self):
         """(storage, in-place version) of every parameter: load_state_dict / in-place edits bump
@@ -79,6 +95,8 @@ class _NativeNet(nn.Module):
         net = self._native_net
         if net is None or net.device != device_index:
             net = rt.Net(self.KIND, device_index)
+            if self._native_precision is not None:
+                net.set_precision(self._native_precision)
             object.__setattr__(self, "_native_net", net)
             object.__setattr__(self, "_native_key", None)
         key = self._param_key()

@@ -301,10 +301,18 @@ def main():
     ap.add_argument("--c5-overlap-only", action="store_true")
     ap.add_argument("--raw-hand-maps", dest="designed_hands", action="store_false",
                     help="C3: run the hand post on the raw net maps instead of designed maps")
+    ap.add_argument("--precision", choices=["fp32", "fp16"], default=None,
+                    help="precision of the x3 convs of every net (rt.Net.set_precision): fp32 = three fp16 "
+                         "products per multiply-add (fp32-accurate, the default), fp16 = one (faster, ~2e-3 "
+                         "of the maps' maximum in error); default: the library's (env ISLPOSE_PRECISION)")
     a = ap.parse_args()
+    if a.precision:
+        os.environ["ISLPOSE_PRECISION"] = a.precision   # read by every net at its creation
     for name, fn in (("c3", c3), ("c4", c4), ("c5", c5), ("c6", c6), ("frame", frame)):
         if a.config in (name, "all"):
-            print(json.dumps(fn(a)), flush=True)
+            res = fn(a)
+            res["precision"] = os.environ.get("ISLPOSE_PRECISION", "fp32")
+            print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":

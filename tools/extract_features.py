@@ -38,6 +38,10 @@ def main():
     ap.add_argument("--no-json", action="store_true", help="skip per-frame JSON files (throughput runs)")
     ap.add_argument("--no-export", action="store_true",
                     help="leave out the get_bodypose/get_handpose columns (the reference raises on >2 hands there)")
+    ap.add_argument("--precision", choices=["fp32", "fp16"], default=None,
+                    help="precision of the body and hand nets' convolutions (Body / Hand precision=): fp16 = one "
+                         "fp16 product per multiply-add instead of three, faster, ~2e-3 of the maps' maximum in "
+                         "error; default: the library's (fp32 unless ISLPOSE_PRECISION=fp16)")
     a = ap.parse_args()
 
     import torch
@@ -61,8 +65,8 @@ def main():
             return path
         return {k: torch.from_numpy(v) for k, v in synth.synth_weights(kind).items()}
 
-    body = Body(weights(a.body_weights, 0), "body25")
-    hand = Hand(weights(a.hand_weights, 2))
+    body = Body(weights(a.body_weights, 0), "body25", precision=a.precision)
+    hand = Hand(weights(a.hand_weights, 2), precision=a.precision)
     model = ISLSignPos(body.model, hand.model)
 
     if a.synthetic:
