@@ -67,6 +67,23 @@ enum isl_algo { ISL_ALGO_X3 = 0, ISL_ALGO_WINO = 1, ISL_ALGO_DIRECT = 2 };
  * Under ISL_ALGO_WINO / ISL_ALGO_DIRECT the value is stored and has no effect. */
 enum isl_precision { ISL_PREC_FP32 = 0, ISL_PREC_FP16 = 1 };
 
+/* Storage of the activations between the ISL_ALGO_X3 convolutions of ISL_PREC_FP16 (not in the
+ * reference; a switch of its own, orthogonal to the precision):
+ *   ISL_ACT_FP32   every arena buffer holds fp32 -- the default, nothing changes;
+ *   ISL_ACT_FP16   the arena buffers between the convs hold fp16: a one-term kernel rounds
+ *                  every activation to fp16 (round to nearest even) before its first use
+ *                  anyway, so its producer stores that rounding -- the same value whoever
+ *                  computes it, and max-pooling commutes with a monotone rounding -- and the
+ *                  net's outputs are the same bits as with ISL_ACT_FP32.  The net input and
+ *                  the net outputs stay fp32 (the outputs unrounded, in buffers of their own);
+ *                  the activation buffers and the epilogues' writes halve.  Opt-in.
+ * The value takes effect only under ISL_ALGO_X3 with ISL_PREC_FP16; otherwise it is stored and
+ * has no effect.  It is all or nothing per run: where any conv of a run would take a kernel
+ * without an fp16-storage form (K ranges across blocks -- split-K and the wave-range kernel --
+ * i.e. the small latency-bound grids, and the 96-pixel small 7x7 tiles), the whole run uses an
+ * fp32 arena exactly as under ISL_ACT_FP32 (isl_net_act_storage_active then reports 0). */
+enum isl_act_storage { ISL_ACT_FP32 = 0, ISL_ACT_FP16 = 1 };
+
 typedef struct isl_net isl_net;
 
 int isl_abi_version(void);
@@ -129,6 +146,7 @@ int isl_net_run(isl_net* net, float* d_out0, float* d_out1, void* stream);
  * role there).  A net keeps one arena per net input size (h, w), sized by
  * capacity: a batch of n frames reuses an arena holding n' >= n frames, and a
  * larger n replaces it.  Arenas of other sizes are evicted least-recently-used
+ * (ISL_ACT_FP16 runs keep arenas of their own per size, counted here like the others)
  * once the net's arenas would exceed the byte budget (env ISLPOSE_ARENA_BUDGET_MB,
  * default 65536; the arena in use is never evicted).  Reports the bytes held and
  * the number of arenas. */
@@ -149,6 +167,17 @@ int isl_net_get_algo(const isl_net* net);
  * launches and reports the FLOPs they execute (one product per multiply-add). */
 int isl_net_set_precision(isl_net* net, int precision);
 int isl_net_get_precision(const isl_net* net);
+
+/* Select the activation storage of a net (default ISL_ACT_FP32, or the env
+ * ISLPOSE_ACT_STORAGE=fp32|fp16 at create time); any other value -> ISL_E_ARG.  Arenas are
+ * kept per (net size, storage), so switching back and forth reallocates nothing, and captured
+ * graphs are keyed by the storage.  The range guard is unchanged: an epilogue checks the fp32
+ * value before it rounds it, and the ISL_ALGO_DIRECT recompute runs on an fp32 arena.
+ * isl_net_act_storage_active: 1 if the last run (or, before it, the last isl_net_preprocess*)
+ * used fp16 activation buffers, else 0. */
+int isl_net_set_act_storage(isl_net* net, int storage);
+int isl_net_get_act_storage(const isl_net* net);
+int isl_net_act_storage_active(const isl_net* net);
 
 /* K ranges of the ISL_ALGO_X3 convolutions (latency of small grids such as batch-1
  * frames; not in the reference, whose torch conv runs per frame):
@@ -218,7 +247,7 @@ int isl_net_timing(isl_net* net, int max_ops, int* n_ops, int* n_runs, double* o
 /* Diagnostic: the ops of the net's graph (convs by their caffe layer name, pools as
  * "maxpool2") and, for the last isl_net_run / isl_net_forward, which conv kernel variant
  * each ran: for ISL_ALGO_X3 convs the variant code of csrc/internal.h x3_variant_code
- * (VAR bits: 2 one-term fp16 products (ISL_PREC_FP16), 512 row union, 1024 in-block K ranges, 2048 split-K, 4096 two pairs per
+ * (VAR bits: 1 reads or writes fp16 activations (ISL_ACT_FP16), 2 one-term fp16 products (ISL_PREC_FP16), 512 row union, 1024 in-block K ranges, 2048 split-K, 4096 two pairs per
  * step, 8192 folds its producers' split-K partials, 32768 pooled-input staging, 65536 one
  * input buffer, 131072 16x16x32 row union, 262144 conv1_1 kernel, 524288 split-K partials
  * left to its consumers (no reduce launch);

@@ -39,6 +39,13 @@
 // accumulator tiles x 3 MFMAs.
 //
 // Variants (template VAR bits):
+//   1     fp16 activation storage (isl_net_set_act_storage ISL_ACT_FP16, opt-in; with 2 only): the input
+//         and output buffers hold the fp16 roundings the one-term staging would have computed (same
+//         layout, 2 B elements), so the staging copies 16 B per pixel-chunk without converting (the
+//         pooled-input form takes packed fp16 row-pair maxima) and the epilogue stores RNE(v), 8 B per
+//         4 channels, after the range check on the fp32 value; a layer writing a net output also stores
+//         the fp32 values (X3Args::out32).  Same tiles, K order and MFMA operands: the same bits as 2
+//         alone.  Combines with every bit 2 does but 2048 (and 8192);
 //   2     one-term fp16 products (isl_net_set_precision ISL_PREC_FP16, opt-in): x*w ~= x_hi*w_hi alone,
 //         one MFMA per tap; every layout below loses its [hi|lo] dimension (hi-only weight slabs,
 //         inputs rounded once at staging), everything else -- tiles, K order, ranges, epilogue and
@@ -118,6 +125,14 @@ struct X3Args {
   // pixels, blocks [nb_full, nblocks) the frame's rest in tail_tiles tiles of ttpx pixels (0: one
   // tiling of px_tiles tiles)
   int nb_full, full_tiles, tail_tiles, ttpx;
+  // VAR 1 (fp16 activation storage), a layer that writes a net output: the unrounded fp32 values
+  // also go to this fp32 buffer (null: none), channels from 0, its own strides and ring
+  float* out32;
+  long long out32_fs, out32_chs;
+  int out32_pad;
+  // VAR 1, the row union: stage plain input runs by LDS-DMA instead of through registers
+  // (x3_a16_dma; every other loop keeps register staging)
+  int xdma;
 };
 
 // u / d for 0 <= u < 2^20, d >= 1, through the fp32 reciprocal r = 1/d: (u + 0.5) / d sits
@@ -174,6 +189,58 @@ __device__ __forceinline__ f16x8 x3_hi8(const f32x4& a, const f32x4& b) {
     hi[2 * k] = h.x; hi[2 * k + 1] = h.y;
   }
   return hi;
+}
+
+// VAR 1 (fp16 activation storage).  One staged pixel-chunk -- 8 channels at element offset e of the
+// buffer `in` -- into a staging register pair: 2 x 16 B of fp32, or (A16) the 16 B of stored fp16
+// roundings, carried in r0 as raw bits (r1 unused)
+template <bool A16>
+__device__ __forceinline__ void x3_ld8(const float* in, size_t e, f32x4& r0, f32x4& r1) {
+  if constexpr (A16) {
+    r0 = *(const f32x4*)((const _Float16*)in + e);
+    r1 = f32x4{0.f, 0.f, 0.f, 0.f};
+  } else {
+    r0 = *(const f32x4*)(in + e);
+    r1 = *(const f32x4*)(in + e + 4);
+  }
+}
+// ... and the one-term B operand of such a pair: rounded here, or (A16) as stored
+template <bool A16>
+__device__ __forceinline__ f16x8 x3_op8(const f32x4& r0, const f32x4& r1) {
+  if constexpr (A16) return __builtin_bit_cast(f16x8, r0);
+  else return x3_hi8(r0, r1);
+}
+// x3_vin_load on an fp16 pair-max buffer: the packed fp16 max of the row pair (the rounding of
+// the fp32 max: the rounding is monotone), zero on the ring; raw bits as x3_ld8<true>
+__device__ __forceinline__ f32x4 x3_vin_load16(const float* src, int yy, int xx, const X3Args& a) {
+  const int y = yy - a.in_pad, x = xx - a.in_pad;
+  const bool in = y >= 0 && y < a.H && x >= 0 && x < a.W;
+  // (ring items read pixel (0, 0) and drop it: no branch around the loads)
+  const _Float16* p0 = (const _Float16*)src + (in ? ((size_t)(2 * y) * a.W + x) * 8 : 0);
+  const f32x4 r0 = *(const f32x4*)p0, r1 = *(const f32x4*)(p0 + (size_t)a.W * 8);
+  f32x4 m;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    // (scalars first: __builtin_bit_cast of a vector element expression reads element 0, hipcc 7)
+    const float a0 = r0[k], a1 = r1[k];
+    const f16x2 c = __builtin_elementwise_max(__builtin_bit_cast(f16x2, a0), __builtin_bit_cast(f16x2, a1));
+    m[k] = in ? __builtin_bit_cast(float, c) : 0.f;
+  }
+  return m;
+}
+// four channels of one output pixel at element offset e of `out`, the first nv (1..4) real:
+// RNE to fp16, 8 B
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void x3_store4h(float* out, size_t e, const f32x4& v, int nv) {
+  _Float16* p = (_Float16*)out + e;
+  const f16x4 hv = __builtin_convertvector(v, f16x4);
+  if (nv >= 4) {
+    *(f16x4*)p = hv;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      if (k < nv) p[k] = hv[k];
+  }
 }
 
 // Split-K reduction: the ranges' sums added in range order (the order of the in-block
@@ -283,6 +350,10 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
   // plane is packed, fetched or staged (NH operand planes instead of two)
   constexpr bool F16 = (VAR & X3V_F16) != 0;
   constexpr int NH = F16 ? 1 : 2;
+  // VAR 1: fp16 activation storage (x3_ld8 / x3_op8 / x3_store4h) -- in and out are fp16 buffers
+  constexpr bool A16 = (VAR & X3V_A16) != 0;
+  static_assert(!A16 || F16, "fp16 activation storage: the one-term kernels");
+  static_assert(!A16 || !(VAR & (16 | 2048 | 8192 | 16384 | 131072)), "fp16 activation storage: no split-K / fold / fused pair form");
   constexpr int WSLAB1 = KS * NH * 2 * BCO;      // one pair: [kx][hi|lo][h][BCO]
   constexpr int WSLAB = PPS * WSLAB1;            // 16-byte units per step
   constexpr int SEGP = SEGMAX + 1;               // + one dummy slot idle staging items write to
@@ -377,7 +448,8 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
   const int La = (ya + a.in_pad) * Wi + xa + a.in_pad;
   const int Lb = (yb + a.in_pad) * Wi + xb + a.in_pad;
   const int seg = Lb - La + 2 * P + 1;
-  const float* in_f = a.in + (size_t)n * a.in_fs;
+  // (A16: an fp16 buffer; in_f then carries its address, every offset from it is in elements)
+  const float* in_f = A16 ? (const float*)((const _Float16*)a.in + (size_t)n * a.in_fs) : a.in + (size_t)n * a.in_fs;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int grp = G2 ? __builtin_amdgcn_readfirstlane(wave / NWAVES) : 0;   // K group (VAR 32)
@@ -676,16 +748,18 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
     auto load_c = [&](int c2, int ky) __attribute__((always_inline)) {
       if (c_px[ky] >= 0) {
         const int c = min(2 * c2 + c_ih[ky], a.cin_chunks - 1);
-        if constexpr (VIN) {   // padded (row, column) of the item, recomputed (no registers held across the loop)
+        if constexpr (VIN && A16) {
+          const int u = (int)ubase + c_px[ky], yy = x3_div(u, inv_wi);
+          ru[0] = x3_vin_load16((const float*)((const _Float16*)in_f + (size_t)c * a.in_chs), yy, u - yy * Wi, a);
+          ru[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        } else if constexpr (VIN) {   // padded (row, column) of the item, recomputed (no registers held across the loop)
           const int u = (int)ubase + c_px[ky], yy = x3_div(u, inv_wi);
           float4 l4, h4;
           x3_vin_load(in_f + (size_t)c * a.in_chs, yy, u - yy * Wi, a, l4, h4);
           ru[0] = f32x4{l4.x, l4.y, l4.z, l4.w};
           ru[1] = f32x4{h4.x, h4.y, h4.z, h4.w};
         } else {
-          const float* src = in_f + (size_t)c * a.in_chs + (size_t)(ubase + c_px[ky]) * 8;
-          ru[0] = *(const f32x4*)src;
-          ru[1] = *(const f32x4*)(src + 4);
+          x3_ld8<A16>(in_f, (size_t)c * a.in_chs + (size_t)(ubase + c_px[ky]) * 8, ru[0], ru[1]);
         }
       }
     };
@@ -695,7 +769,7 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
       // weights are zero (pack_x3), and the staged values are finite (range-checked), so
       // it adds exact zeros
       if constexpr (F16) {
-        const f16x8 hi = x3_hi8(ru[0], ru[1]);
+        const f16x8 hi = x3_op8<A16>(ru[0], ru[1]);
         const int px = c_px[ky] < 0 ? SEGUP - 1 : c_px[ky];
         sx[c_ih[ky] * SEGUP + px] = hi;
       } else {
@@ -717,6 +791,31 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
                                            (__attribute__((address_space(3))) void*)(dst + q * 64), 16, 0, 0);
       }
     };
+    // A16, plain runs (a.xdma): the fp16 union run is the LDS image itself ([h][px] x 16 B), so the
+    // loader waves copy their third of it by LDS-DMA -- 1 KiB pieces of the [h][px] slab, one per
+    // loader wave and ky step, no VGPRs, no conversion.  Every lane is live: a piece past the slab's
+    // end is moved back onto it, a unit past the run re-reads the run's last pixel into a slot no
+    // tap reads, and a missing odd chunk re-reads the last real one (as load_c).  Measured against
+    // register staging in the net (Mode N, profiles/act16/ops_n_*): -2 to -4 % on the 92x164 layers,
+    // -1 % on the 46x82 stage layers.  The same copy in the generic two-buffer loop measured 7-11 %
+    // slower than its register staging (conv1_2, the 1x1 layers) and is not built.
+    constexpr int NPU = (XSLABU + 63) / 64, PPK = (NPU + KS - 1) / KS;
+    static_assert(!A16 || (PPK <= LOADER_WAVES && XSLABU >= 64), "union DMA pieces: one per loader wave and step");
+    const bool xdma = A16 && !VIN && a.xdma;     // (uniform)
+    auto issue_u = [&](int c2, int ky, int bx) __attribute__((always_inline)) {
+      if constexpr (A16 && !VIN) {
+        const int p = ky * PPK + wave_u;
+        if (wave_u < PPK && p < NPU) {
+          const int base = min(p * 64, XSLABU - 64);
+          const int j = base + lane, ihh = j >= SEGUP ? 1 : 0, px = min(j - ihh * SEGUP, segu - 1);
+          const int c = min(2 * c2 + ihh, a.cin_chunks - 1);
+          const _Float16* src = (const _Float16*)in_f + (size_t)c * a.in_chs + (size_t)(ubase + px) * 8;
+          __builtin_amdgcn_global_load_lds((const void*)src,
+                                           (__attribute__((address_space(3))) void*)(smem + 2 * WSLAB + bx * XSLABU + base),
+                                           16, 0, 0);
+        }
+      }
+    };
     auto tap_u = [&](int bw, int bx, int ky, int kx) __attribute__((always_inline)) {
       tap(smem + bw * WSLAB + h * BCO + wave_m * WM * 32 + l32,
           smem + 2 * WSLAB + bx * XSLABU + h * SEGUP + ky * Wi, SEGUP, kx);
@@ -725,8 +824,12 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
     if (!loader) issue_c(0, 0);
 #pragma unroll
     for (int ky = 0; ky < KS; ++ky) {
-      load_c(0, ky);
-      store_c(0, ky, 0);
+      if (xdma) {
+        if (loader) issue_u(0, ky, 0);
+      } else {
+        load_c(0, ky);
+        store_c(0, ky, 0);
+      }
     }
     __syncthreads();
     for (int c2 = 0; c2 < a.pairs; ++c2) {
@@ -752,13 +855,16 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
         __builtin_amdgcn_sched_barrier(0);
         tap_u(t & 1, c2 & 1, ky, 0);
         __builtin_amdgcn_sched_barrier(0);
-        if (loader && next) load_c(c2 + 1, ky);   // a third of the next pair's union per step
+        if (loader && next) {                     // a third of the next pair's union per step
+          if (xdma) issue_u(c2 + 1, ky, (c2 + 1) & 1);
+          else load_c(c2 + 1, ky);
+        }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int kx = 1; kx < KS; ++kx) tap_u(t & 1, c2 & 1, ky, kx);
         __builtin_amdgcn_sched_barrier(0);
         stamp(2);
-        if (loader && next) store_c(c2 + 1, ky, (c2 + 1) & 1);
+        if (loader && next && !xdma) store_c(c2 + 1, ky, (c2 + 1) & 1);
         stamp(3);
         __syncthreads();
       }
@@ -850,6 +956,10 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
               raw[i][0] = v0;
               raw[i][1] = v1;
             }
+          } else if constexpr (VIN && A16) {
+            const int u = (int)row + ipx[i], yy = x3_div(u, inv_wi);
+            raw[i][0] = x3_vin_load16((const float*)((const _Float16*)in_f + (size_t)c * a.in_chs), yy, u - yy * Wi, a);
+            raw[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
           } else if constexpr (VIN) {   // padded (row, column) of the item, recomputed per step
             const int u = (int)row + ipx[i], yy = x3_div(u, inv_wi);
             float4 l4, h4;
@@ -857,9 +967,7 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
             raw[i][0] = f32x4{l4.x, l4.y, l4.z, l4.w};
             raw[i][1] = f32x4{h4.x, h4.y, h4.z, h4.w};
           } else {
-            const float* src = in_f + (size_t)c * a.in_chs + (size_t)(row + ipx[i]) * 8;
-            raw[i][0] = *(const f32x4*)src;
-            raw[i][1] = *(const f32x4*)(src + 4);
+            x3_ld8<A16>(in_f, (size_t)c * a.in_chs + (size_t)(row + ipx[i]) * 8, raw[i][0], raw[i][1]);
           }
         } else {
           raw[i][0] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -879,7 +987,7 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
       for (int i = 0; i < IT; ++i) {
         if (ipx[i] < 0) continue;
         if constexpr (F16) {
-          s[ih[i] * SEGP + ipx[i]] = x3_hi8(raw[i][0], raw[i][1]);
+          s[ih[i] * SEGP + ipx[i]] = x3_op8<A16>(raw[i][0], raw[i][1]);
         } else {
           f16x8 hi, lo;
           x3_split8(raw[i][0], raw[i][1], hi, lo);
@@ -1013,9 +1121,7 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
         for (int k = 0; k < ITL; ++k) {
           // a missing odd chunk stages the last real one (its packed weights are zero)
           const int c = min(2 * c2 + lih[k], a.cin_chunks - 1);
-          const float* src = in_f + (size_t)c * a.in_chs + (size_t)(row + max(lpx[k], 0)) * 8;
-          rs[sl][k][0] = *(const f32x4*)src;
-          rs[sl][k][1] = *(const f32x4*)(src + 4);
+          x3_ld8<A16>(in_f, (size_t)c * a.in_chs + (size_t)(row + max(lpx[k], 0)) * 8, rs[sl][k][0], rs[sl][k][1]);
         }
       };
       auto dstore = [&](int xb, int sl) __attribute__((always_inline)) {
@@ -1023,7 +1129,7 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
 #pragma unroll
         for (int k = 0; k < ITL; ++k) {
           if constexpr (F16) {
-            const f16x8 hi = x3_hi8(rs[sl][k][0], rs[sl][k][1]);
+            const f16x8 hi = x3_op8<A16>(rs[sl][k][0], rs[sl][k][1]);
             const int px = lpx[k] < 0 ? SEGP - 1 : lpx[k];
             sx[lih[k] * SEGP + px] = hi;
           } else {
@@ -1341,7 +1447,8 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
   // PReLU slopes come from LDS (staged once), so no global load -- and no vmcnt(0)
   // behind the stores issued so far -- sits between the output stores.
   const int Wo = a.hpool ? a.W / 2 : a.W + 2 * a.out_pad;
-  float* out_f = a.out + (size_t)n * a.out_fs;
+  // (A16: an fp16 buffer addressed in elements from out_f's address, x3_store4h)
+  float* out_f = A16 ? (float*)((_Float16*)a.out + (size_t)n * a.out_fs) : a.out + (size_t)n * a.out_fs;
   bool bad = false;
 #ifdef ISLPOSE_DEV
   // ablations (tools/convbench, ISLPOSE_X3_ABL): 64 no epilogue at all, 32 no bias load
@@ -1362,8 +1469,8 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
     const int m = m0 + (wave_n * WN + wn) * 32 + l32;
     if (m > mlast) continue;
     const int y = m / a.W, x = m - y * a.W;
-    float* op = a.hpool ? out_f + (size_t)(y * Wo + (x >> 1)) * 8
-                        : out_f + (size_t)((y + a.out_pad) * Wo + x + a.out_pad) * 8;
+    const size_t ope = a.hpool ? (size_t)(y * Wo + (x >> 1)) * 8 : (size_t)((y + a.out_pad) * Wo + x + a.out_pad) * 8;
+    float* op = out_f + ope;                      // (fp32 buffers)
 #pragma unroll
     for (int wm = 0; wm < WM; ++wm) {
       const int cob = co_t * BCO + (wave_m * WM + wm) * 32 + 4 * h;
@@ -1391,6 +1498,24 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
           for (int e = 0; e < 4; ++e)
             v[e] = fmaxf(v[e], __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v[e]), 0xB1, 0xF, 0xF, false)));
           if (x & 1) continue;
+        }
+        if constexpr (A16) {
+          // the stored rounding is the one the consumers' staging would have made of v; a net
+          // output also keeps v itself (fp32, a buffer of its own)
+          if (co < a.cout) x3_store4h(out_f, ope + (size_t)(co >> 3) * a.out_chs + (co & 7), v, a.cout - co);
+          if (a.out32) {
+            const int W32 = a.W + 2 * a.out32_pad;
+            float* o32 = a.out32 + (size_t)n * a.out32_fs + (size_t)(co >> 3) * a.out32_chs +
+                         (size_t)((y + a.out32_pad) * W32 + x + a.out32_pad) * 8 + (co & 7);
+            if (co + 3 < a.cout) {
+              *(f32x4*)o32 = v;
+            } else {
+#pragma unroll
+              for (int e = 0; e < 4; ++e)
+                if (co + e < a.cout) o32[e] = v[e];
+            }
+          }
+          continue;
         }
         float* oc = op + (size_t)(co >> 3) * a.out_chs + (co & 7);
         if (co + 3 < a.cout) {
@@ -1426,9 +1551,11 @@ static thread_local int t_last_variant = 0;
 int x3_last_variant() { return t_last_variant; }
 
 // F16 (ISL_PREC_FP16): one-term products -- hi-only filters [kk][h][64][8] (pack_hi_only of pack_x3_rgb) and an
-// im2col tile of the hi halves alone
-template <int RGB_BPX, bool F16>
+// im2col tile of the hi halves alone.  O16 (ISL_ACT_FP16, with F16): the fp32 net input as ever, the
+// output stored as fp16 (x3_store4h) after the range check on the fp32 value
+template <int RGB_BPX, bool F16, bool O16 = false>
 __global__ void __launch_bounds__(RGB_BPX, 1) conv_x3_rgb(X3Args a) {
+  static_assert(!O16 || F16, "fp16 activation storage: the one-term kernel");
   constexpr int RGB_NT = RGB_BPX;
   constexpr int NH = F16 ? 1 : 2;
   __shared__ f16x8 s_x[NH][4][RGB_BPX];         // [hi|lo][k chunk q][px]
@@ -1509,14 +1636,15 @@ __global__ void __launch_bounds__(RGB_BPX, 1) conv_x3_rgb(X3Args a) {
   }
   // epilogue (as conv_x3_f16's): x 2^-s, bias, activation, range check, float4 stores
   const int Wo = a.W + 2 * a.out_pad;
-  float* out_f = a.out + (size_t)n * a.out_fs;
+  float* out_f = O16 ? (float*)((_Float16*)a.out + (size_t)n * a.out_fs) : a.out + (size_t)n * a.out_fs;
   bool bad = false;
 #pragma unroll
   for (int wn = 0; wn < 2; ++wn) {
     const int m = m0 + wave * 64 + wn * 32 + l32;
     if (m > mlast) continue;
     const int y = m / a.W, x = m - y * a.W;
-    float* op = out_f + (size_t)((y + a.out_pad) * Wo + x + a.out_pad) * 8;
+    const size_t ope = (size_t)((y + a.out_pad) * Wo + x + a.out_pad) * 8;
+    float* op = out_f + ope;                      // (fp32 buffers)
 #pragma unroll
     for (int wm = 0; wm < 2; ++wm) {
 #pragma unroll
@@ -1530,6 +1658,10 @@ __global__ void __launch_bounds__(RGB_BPX, 1) conv_x3_rgb(X3Args a) {
           if (a.act == ACT_RELU) v[e] = v[e] > 0.f ? v[e] : 0.f;
           else if (a.act == ACT_PRELU) v[e] = v[e] >= 0.f ? v[e] : v[e] * s_b[RGB_BCO + co + e];
           bad |= !(__builtin_fabsf(v[e]) < 65504.f);
+        }
+        if constexpr (O16) {
+          x3_store4h(out_f, ope + (size_t)(co >> 3) * a.out_chs + (co & 7), v, a.cout - co);
+          continue;
         }
         float* oc = op + (size_t)(co >> 3) * a.out_chs + (co & 7);
         if (co + 3 < a.cout) {
@@ -1559,8 +1691,12 @@ hipError_t launch_conv_x3_rgb(const ConvLaunch& c, hipStream_t s) {
   a.out_chs = (long long)(c.H + 2 * c.out_pad) * (c.W + 2 * c.out_pad) * 8;
   a.in_fs = a.in_chs * (c.in_cs / 8);
   a.out_fs = a.out_chs * (c.out_cs / 8);
+  if (c.act16 && (!c.f16 || c.out32)) {
+    set_error("conv_x3_rgb: fp16 activation storage needs the one-term form (and is no net output)");
+    return hipErrorInvalidValue;
+  }
   a.in = c.in + (c.in_coff / 8) * a.in_chs;
-  a.out = c.out + (c.out_coff / 8) * a.out_chs;
+  a.out = c.act16 ? (float*)((_Float16*)c.out + (c.out_coff / 8) * a.out_chs) : c.out + (c.out_coff / 8) * a.out_chs;
   a.wpk = (const f16x8*)c.wx3; a.bias = c.bias; a.slope = c.slope;
   a.range_flag = c.range_flag;
   a.wscale_inv = c.wscale_inv;
@@ -1578,8 +1714,9 @@ hipError_t launch_conv_x3_rgb(const ConvLaunch& c, hipStream_t s) {
   const long long nb = (long long)c.n * a.px_tiles;
   if (nb <= 0 || nb > 0x7fffffff) { set_error("conv_x3_rgb: bad grid"); return hipErrorInvalidValue; }
   a.nblocks = (int)nb;
-  t_last_variant = x3_variant_code(X3V_RGB | (c.f16 ? X3V_F16 : 0), 3, bpx, RGB_BCO);
-  if (c.f16) hipLaunchKernelGGL((conv_x3_rgb<bpx, true>), dim3(a.nblocks), dim3(bpx), 0, s, a);
+  t_last_variant = x3_variant_code(X3V_RGB | (c.f16 ? X3V_F16 : 0) | (c.act16 ? X3V_A16 : 0), 3, bpx, RGB_BCO);
+  if (c.act16) hipLaunchKernelGGL((conv_x3_rgb<bpx, true, true>), dim3(a.nblocks), dim3(bpx), 0, s, a);
+  else if (c.f16) hipLaunchKernelGGL((conv_x3_rgb<bpx, true>), dim3(a.nblocks), dim3(bpx), 0, s, a);
   else hipLaunchKernelGGL((conv_x3_rgb<bpx, false>), dim3(a.nblocks), dim3(bpx), 0, s, a);
   return hipGetLastError();
 }
@@ -1836,6 +1973,13 @@ static void x3_tail_plan(int n, int HW, X3Args& a) {
   }
 }
 
+// fp16 activation storage (VAR 1): the row union stages its plain input runs by LDS-DMA.
+// ISLPOSE_A16_DMA=0: through registers, as every other loop (A/B; read per launch).
+static bool x3_a16_dma() {
+  const char* e = getenv("ISLPOSE_A16_DMA");
+  return !(e && e[0] == '0');
+}
+
 template <int KS, int WAVES_M, int WAVES_N, int WM, int WN, int VAR, int OCC>
 static hipError_t launch_t(const ConvLaunch& c, hipStream_t s) {
   constexpr int BCO = WAVES_M * WM * 32;
@@ -1843,6 +1987,14 @@ static hipError_t launch_t(const ConvLaunch& c, hipStream_t s) {
   // (the fused pair's 512-channel tile does not fit the 4-bit tile field: it records BCO / 2,
   // decode_variant doubles it back for VAR 16)
   t_last_variant = x3_variant_code(VAR, KS, BPX, (VAR & 16) ? BCO / 2 : BCO);
+  constexpr bool A16 = (VAR & X3V_A16) != 0;
+  // the variants without an fp16-storage form (x3_act16_ok: the runtime never plans them)
+  if constexpr (A16 && ((VAR & (16 | 2048 | 8192 | 16384 | 131072)) != 0 || (KS == 7 && WAVES_N == 3))) {
+    set_error("conv_x3: no fp16-storage form of this variant (x3_act16_ok)");
+    return hipErrorInvalidValue;
+  } else {
+  if (A16 != (c.act16 != 0)) { set_error("conv_x3: fp16-storage variant mismatch"); return hipErrorInvalidValue; }
+  if (c.out32 && (!A16 || c.hpool || (c.out32_cs & 7))) { set_error("conv_x3: fp32 output copy outside fp16 storage"); return hipErrorInvalidValue; }
   constexpr int P = KS / 2;
   constexpr int SEGCAP = x3_segmax(BPX);
   constexpr bool SPLIT = (VAR & 2048) != 0, RANGED = (VAR & 1024) != 0;
@@ -1897,6 +2049,15 @@ static hipError_t launch_t(const ConvLaunch& c, hipStream_t s) {
   a.out_fs = a.out_chs * (c.out_cs / 8);
   a.in = c.in + (c.in_coff / 8) * a.in_chs;
   a.out = c.out + (c.out_coff / 8) * a.out_chs;
+  if constexpr (A16) {   // fp16 buffers: the slice offsets in 2-byte elements
+    a.in = (const float*)((const _Float16*)c.in + (c.in_coff / 8) * a.in_chs);
+    a.out = (float*)((_Float16*)c.out + (c.out_coff / 8) * a.out_chs);
+    a.out32 = c.out32;
+    a.out32_pad = c.out32_pad;
+    a.out32_chs = (long long)(c.H + 2 * c.out32_pad) * (c.W + 2 * c.out32_pad) * 8;
+    a.out32_fs = a.out32_chs * (c.out32_cs / 8);
+    a.xdma = x3_a16_dma() ? 1 : 0;
+  }
   a.wpk = (const f16x8*)c.wx3; a.bias = c.bias; a.slope = c.slope;
   a.range_flag = c.range_flag;
   a.wscale_inv = c.wscale_inv;
@@ -1937,6 +2098,7 @@ static hipError_t launch_t(const ConvLaunch& c, hipStream_t s) {
     if (c.fold_out) { set_error("conv_x3: fold_out without split-K across blocks"); return hipErrorInvalidValue; }
   }
   return hipGetLastError();
+  }
 }
 
 static bool x3_small_tiles() {
@@ -2279,7 +2441,8 @@ static X3Ranges x3_ranges(const ConvLaunch& c) {
 }
 
 // FV: X3V_F16 for the one-term form of every variant (ISL_PREC_FP16: the same plan, tiles and K
-// order on hi-only operands), 0 for the three-term kernels
+// order on hi-only operands), X3V_F16 | X3V_A16 for its fp16-storage form (ISL_ACT_FP16), 0 for the
+// three-term kernels
 template <int KS, int FV>
 static hipError_t launch_ks(const ConvLaunch& c, hipStream_t s) {
   if constexpr (KS == 3) {
@@ -2561,8 +2724,8 @@ static hipError_t launch_wr_t(const ConvLaunch& c, int S, hipStream_t s) {
   if (c.in_pad < P) { set_error("conv_x3_wr: input ring narrower than kernel radius"); return hipErrorInvalidValue; }
   if ((c.in_cs | c.in_coff | c.out_cs | c.out_coff) & 7) { set_error("conv_x3_wr: slice not on a chunk"); return hipErrorInvalidValue; }
   if (!c.wx3 || !c.range_flag) { set_error("conv_x3_wr: split weights / range flag missing"); return hipErrorInvalidValue; }
-  if (c.hpool || c.vin || c.fold || c.fold_out || c.cout7 > 0) {
-    set_error("conv_x3_wr: plain layers only (no fused pool, fold or pair)");
+  if (c.hpool || c.vin || c.fold || c.fold_out || c.cout7 > 0 || c.act16) {
+    set_error("conv_x3_wr: plain layers only (no fused pool, fold, pair or fp16 storage)");
     return hipErrorInvalidValue;
   }
   const int pairs = (c.cin_chunks + 1) / 2;
@@ -2608,7 +2771,29 @@ static hipError_t launch_x3_wr(const ConvLaunch& c, int S, hipStream_t s) {
   return hipErrorInvalidValue;
 }
 
+bool x3_act16_ok(const ConvLaunch& c0) {
+  if (!c0.f16 || c0.cout7 > 0 || c0.fold || c0.fold_out || !x3_fits(c0)) return false;
+  if (c0.ks != 1 && c0.ks != 3 && c0.ks != 7) return false;
+  ConvLaunch c = c0;
+  const X3Ranges r = x3_ranges(c);
+  c.ksplit = r.S;
+  c.ws = nullptr;
+  // K ranges across blocks (the wave-range kernel or split-K + x3_splitk_reduce) and the A/B
+  // mode that runs the other small grids on the wave-range kernel
+  if (r.across_blocks || x3_wr_mode() == 2) return false;
+  if (c.ks == 7 && c.ksplit <= 1 && c.bco == 128 && x3_small7(c) && x3_small7_96(c)) return false;
+  return true;
+}
+
 hipError_t launch_conv_x3(const ConvLaunch& c0, hipStream_t s) {
+  if (c0.act16 && !x3_act16_ok(c0)) {
+    set_error("conv_x3: launch without an fp16-storage form (the runtime plans such runs on fp32 buffers)");
+    return hipErrorInvalidValue;
+  }
+  if (c0.out32 && !c0.act16) {
+    set_error("conv_x3: fp32 output copy outside fp16 storage");
+    return hipErrorInvalidValue;
+  }
   if (c0.cout7 > 0 && c0.f16) {
     set_error("conv_x3: the fused 1x1 pair has no one-term form (the plan runs it unfused)");
     return hipErrorInvalidValue;
@@ -2636,9 +2821,9 @@ hipError_t launch_conv_x3(const ConvLaunch& c0, hipStream_t s) {
     c.ws = nullptr;        // in-block ranges (or none)
   }
   switch (c.ks) {
-    case 1: return c.f16 ? launch_ks<1, X3V_F16>(c, s) : launch_ks<1, 0>(c, s);
-    case 3: return c.f16 ? launch_ks<3, X3V_F16>(c, s) : launch_ks<3, 0>(c, s);
-    case 7: return c.f16 ? launch_ks<7, X3V_F16>(c, s) : launch_ks<7, 0>(c, s);
+    case 1: return c.act16 ? launch_ks<1, X3V_F16 | X3V_A16>(c, s) : c.f16 ? launch_ks<1, X3V_F16>(c, s) : launch_ks<1, 0>(c, s);
+    case 3: return c.act16 ? launch_ks<3, X3V_F16 | X3V_A16>(c, s) : c.f16 ? launch_ks<3, X3V_F16>(c, s) : launch_ks<3, 0>(c, s);
+    case 7: return c.act16 ? launch_ks<7, X3V_F16 | X3V_A16>(c, s) : c.f16 ? launch_ks<7, X3V_F16>(c, s) : launch_ks<7, 0>(c, s);
   }
   set_error("conv_x3: unsupported kernel size");
   return hipErrorInvalidValue;

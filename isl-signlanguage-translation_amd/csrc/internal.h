@@ -14,12 +14,18 @@ namespace isl {
 // for a K step of 8 channels reads whole cache lines.  Convolutions read/write
 // channel slices [coff, coff+C) (coff a multiple of 8) of such buffers, which is
 // how every torch.cat of the reference becomes zero-copy.
+// esize 2 (ISL_ACT_FP16, an fp16-storage arena): the same layout with fp16 elements -- `base`
+// then points at _Float16 values, every element offset is unchanged.  The net input, the net
+// outputs (buffers of their own there, runtime.cpp) and the split-K / fold workspaces are fp32
+// in every arena; only the kernels with an fp16-storage form (ConvLaunch::act16, the *16 pool
+// launches) read or write an esize-2 buffer.
 struct Act {
   float* base = nullptr;
   int n = 0, H = 0, W = 0, pad = 0, cs = 0;   // cs: channel capacity, a multiple of 8
+  int esize = 4;                              // bytes per element: 4 (fp32) or 2 (fp16)
   size_t chunk_elems() const { return (size_t)(H + 2 * pad) * (W + 2 * pad) * 8; }
   size_t frame_elems() const { return chunk_elems() * (cs / 8); }
-  size_t bytes() const { return frame_elems() * n * sizeof(float); }
+  size_t bytes() const { return frame_elems() * n * (size_t)esize; }
 };
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_PRELU = 2 };
@@ -58,6 +64,14 @@ struct ConvLaunch {
   // layouts without their [hi|lo] dimension (runtime.cpp pack_hi_only) -- and the kernels
   // round the activations to fp16 once at staging; launch_conv_x3, launch_conv_x3_rgb only
   int f16 = 0;
+  // ISL_ACT_FP16 (with f16 only): `in` and `out` are fp16 buffers (Act::esize 2; the strides in
+  // elements are the same), the staging copies the stored roundings and the epilogue stores
+  // RNE(v) after its range check on the fp32 value.  launch_conv_x3_rgb reads its fp32 net input
+  // as ever and writes fp16.  out32 (a layer that writes a net output): the unrounded fp32
+  // values also go to channels [0, cout) of this fp32 buffer of out32_cs channels, ring out32_pad
+  int act16 = 0;
+  float* out32 = nullptr;
+  int out32_pad = 0, out32_cs = 0;
   // split-K workspace (conv_x3 on grids too small to fill the GPU); null = no split
   float* ws = nullptr;
   size_t ws_floats = 0;
@@ -129,10 +143,15 @@ hipError_t launch_conv_x3_c12(const ConvLaunch& l1, const ConvLaunch& l2, hipStr
 double conv_x3_c12_mfma_flops(const ConvLaunch& l1);
 hipError_t launch_conv_x3(const ConvLaunch& c, hipStream_t s);
 bool x3_fits(const ConvLaunch& c);
+// whether launch_conv_x3 would run c (f16 set, the fields as at its launch) on a kernel with an
+// fp16-storage form (ConvLaunch::act16): every one-term conv_x3_f16 variant but split-K across
+// blocks, the fold and the 96-pixel small 7x7 tiles; not the wave-range kernel
+bool x3_act16_ok(const ConvLaunch& c);
 // whether launch_conv_x3 can run c with hpool (even W, not split across blocks)
 bool x3_hpool_ok(const ConvLaunch& c);
 double conv_x3_mfma_flops(const ConvLaunch& c);
-// Which conv_x3 variant a launch ran (isl_net_op_info): the template's VAR bits (512 row
+// Which conv_x3 variant a launch ran (isl_net_op_info): the template's VAR bits (1 fp16
+// activation storage, 512 row
 // union, 1024 in-block K ranges, 2048 split-K across blocks, 4096 two pairs per step,
 // 32768 pooled-input staging, 65536 one input buffer), X3V_RGB for conv_x3_rgb, the tile
 // (pixels / 32 at bits 20-24, output channels / 32 at bits 25-28) and the kernel radius
@@ -142,6 +161,7 @@ constexpr int X3V_FOLD_OUT = 1 << 19;   // a split-K producer whose reduce was f
 constexpr int X3V_C12 = 4;              // conv1_1 -> conv1_2 -> pair-max in one launch (conv_c12.hip)
 constexpr int X3V_W2 = 64;              // split-fp16 Winograd F(2x2, 3x3) (wino_f16.hip)
 constexpr int X3V_F16 = 2;              // one-term fp16 products (ISL_PREC_FP16; a template VAR bit too)
+constexpr int X3V_A16 = 1;              // reads / writes fp16 activations (ISL_ACT_FP16; a template VAR bit, with X3V_F16)
 
 constexpr int x3_variant_code(int var, int ks, int bpx, int bco) {
   return (var & 0xfffff) | ((bpx / 32) << 20) | ((bco / 32) << 25) | ((ks / 2) << 29);
@@ -182,6 +202,8 @@ hipError_t launch_range_count(const int* flag, unsigned long long* trips, hipStr
 // second half of a fused 2x2 max-pool: row pairs of a horizontally pooled buffer
 // (ConvLaunch::hpool, [n][chunk][H][W/2][8]) into the padded next buffer
 hipError_t launch_vpool2(const Act& half, const Act& out, int C, hipStream_t s);
+// (both pools take fp16 buffers too -- in and out of one Act::esize; the max of roundings is
+// the rounding of the max)
 hipError_t launch_pack_nchw(const float* x, int n, int C, int h, int w, const Act& out, hipStream_t s);
 hipError_t launch_unpack_nchw(const Act& in, int coff, int C, float* y, hipStream_t s);
 // Pre-processing of a batch of images described by a device table of entries

@@ -32,6 +32,44 @@ __global__ void maxpool2_kernel(const float* __restrict__ in, int ip, int iH, in
   *(f32x4*)(out + ((size_t)f * out_chunks + k) * och + (size_t)((y + op) * oWp + x + op) * 8 + 4 * half) = m;
 }
 
+// The same pool on fp16 buffers (ISL_ACT_FP16, Act::esize 2): the same thread order, 8 B per
+// thread, packed fp16 maxima.  A max of fp16 roundings is the rounding of the fp32 max (the
+// rounding is monotone), so the pooled values are the ones the next conv's staging would have
+// rounded from maxpool2_kernel's output.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f16x4 max4h(const f16x4& a, const f16x4& b) { return __builtin_elementwise_max(a, b); }
+
+__global__ void maxpool2_f16_kernel(const _Float16* __restrict__ in, int ip, int iH, int iW,
+                                    _Float16* __restrict__ out, int op, int oH, int oW, int chunks, int in_chunks,
+                                    int out_chunks) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= oH * oW * 2) return;
+  const int plane = blockIdx.y, f = plane / chunks, k = plane - f * chunks;
+  const int half = idx & 1, px = idx >> 1;
+  const int y = px / oW, x = px - y * oW;
+  const int iWp = iW + 2 * ip, oWp = oW + 2 * op;
+  const size_t ich = (size_t)(iH + 2 * ip) * iWp * 8, och = (size_t)(oH + 2 * op) * oWp * 8;
+  const _Float16* p = in + ((size_t)f * in_chunks + k) * ich + (size_t)((2 * y + ip) * iWp + 2 * x + ip) * 8 + 4 * half;
+  const f16x4 a = *(const f16x4*)p, b = *(const f16x4*)(p + 8);
+  const f16x4 c = *(const f16x4*)(p + (size_t)iWp * 8), d = *(const f16x4*)(p + (size_t)iWp * 8 + 8);
+  *(f16x4*)(out + ((size_t)f * out_chunks + k) * och + (size_t)((y + op) * oWp + x + op) * 8 + 4 * half) =
+      max4h(max4h(a, b), max4h(c, d));
+}
+
+__global__ void vpool2_f16_kernel(const _Float16* __restrict__ in, int iH, int iW2, _Float16* __restrict__ out,
+                                  int op, int oH, int oW, int chunks, int in_chunks, int out_chunks) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= oH * oW * 2) return;
+  const int plane = blockIdx.y, f = plane / chunks, k = plane - f * chunks;
+  const int half = idx & 1, px = idx >> 1;
+  const int y = px / oW, x = px - y * oW;
+  const int oWp = oW + 2 * op;
+  const size_t ich = (size_t)iH * iW2 * 8, och = (size_t)(oH + 2 * op) * oWp * 8;
+  const _Float16* p = in + ((size_t)f * in_chunks + k) * ich + (size_t)(2 * y * iW2 + x) * 8 + 4 * half;
+  const f16x4 a = *(const f16x4*)p, c = *(const f16x4*)(p + (size_t)iW2 * 8);
+  *(f16x4*)(out + ((size_t)f * out_chunks + k) * och + (size_t)((y + op) * oWp + x + op) * 8 + 4 * half) = max4h(a, c);
+}
+
 // Range-guard bookkeeping of isl_net_check_async: a set flag adds one to the net's trip
 // counter (read by isl_net_range_info) before the flag is copied out and reset.
 __global__ void range_count_kernel(const int* __restrict__ flag, unsigned long long* __restrict__ trips) {
@@ -49,6 +87,13 @@ hipError_t launch_maxpool2(const Act& in, const Act& out, int C, hipStream_t s) 
   if (per_plane > 0x7fffffffLL || (long long)out.n * chunks > 65535) {
     set_error("maxpool2: plane too large");
     return hipErrorInvalidValue;
+  }
+  if (in.esize != out.esize) { set_error("maxpool2: mixed element sizes"); return hipErrorInvalidValue; }
+  if (in.esize == 2) {
+    hipLaunchKernelGGL(maxpool2_f16_kernel, dim3((unsigned)((per_plane + 255) / 256), out.n * chunks), dim3(256), 0, s,
+                       (const _Float16*)in.base, in.pad, in.H, in.W, (_Float16*)out.base, out.pad, out.H, out.W, chunks,
+                       in.cs / 8, out.cs / 8);
+    return hipGetLastError();
   }
   hipLaunchKernelGGL(maxpool2_kernel, dim3((unsigned)((per_plane + 255) / 256), out.n * chunks), dim3(256), 0, s,
                      in.base, in.pad, in.H, in.W, out.base, out.pad, out.H, out.W, chunks, in.cs / 8, out.cs / 8);
@@ -85,6 +130,13 @@ hipError_t launch_vpool2(const Act& in, const Act& out, int C, hipStream_t s) {
     set_error("vpool2: bad geometry");
     return hipErrorInvalidValue;
   }
+  if (in.esize != out.esize) { set_error("vpool2: mixed element sizes"); return hipErrorInvalidValue; }
+  if (in.esize == 2) {
+    hipLaunchKernelGGL(vpool2_f16_kernel, dim3((unsigned)((per_plane + 255) / 256), out.n * chunks), dim3(256), 0, s,
+                       (const _Float16*)in.base, in.H, in.W, (_Float16*)out.base, out.pad, out.H, out.W, chunks,
+                       in.cs / 8, out.cs / 8);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(vpool2_kernel, dim3((unsigned)((per_plane + 255) / 256), out.n * chunks), dim3(256), 0, s,
                      in.base, in.H, in.W, out.base, out.pad, out.H, out.W, chunks, in.cs / 8, out.cs / 8);
   return hipGetLastError();
@@ -109,6 +161,7 @@ __global__ void pack_nchw_kernel(const float* __restrict__ x, int n, int C, int 
 hipError_t launch_pack_nchw(const float* x, int n, int C, int h, int w, const Act& out, hipStream_t s) {
   const long long total = (long long)n * h * w;
   const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 16);
+  if (out.esize != 4) { set_error("pack_nchw: the net input is an fp32 buffer"); return hipErrorInvalidValue; }
   hipLaunchKernelGGL(pack_nchw_kernel, dim3(grid), dim3(256), 0, s, x, n, C, h, w, out.base, out.pad, out.cs);
   return hipGetLastError();
 }
@@ -132,6 +185,7 @@ __global__ void unpack_nchw_kernel(const float* __restrict__ in, int ip, int ics
 hipError_t launch_unpack_nchw(const Act& in, int coff, int C, float* y, hipStream_t s) {
   const long long total = (long long)in.n * C * in.H * in.W;
   const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 16);
+  if (in.esize != 4) { set_error("unpack_nchw: fp32 buffers only (net input / outputs)"); return hipErrorInvalidValue; }
   hipLaunchKernelGGL(unpack_nchw_kernel, dim3(grid), dim3(256), 0, s, in.base, in.pad, in.cs, coff, in.n, C,
                      in.H, in.W, y);
   return hipGetLastError();
@@ -238,6 +292,7 @@ __global__ void preprocess_kernel(const uint8_t* __restrict__ frames, const PreS
 hipError_t launch_preprocess_tab(const uint8_t* frames, long long row_bytes, const void* tab, int n, const Act& out,
                                  hipStream_t s) {
   if (n > 65535) { set_error("preprocess: batch too large"); return hipErrorInvalidValue; }
+  if (out.esize != 4) { set_error("preprocess: the net input is an fp32 buffer"); return hipErrorInvalidValue; }
   const int blocks = (int)std::min<long long>(((long long)out.H * out.W + 255) / 256, 1024);
   hipLaunchKernelGGL(preprocess_kernel, dim3(blocks, n), dim3(256), 0, s, frames, (const PreSrc*)tab, row_bytes,
                      out.base, out.pad, out.cs, out.H, out.W);

@@ -191,6 +191,7 @@ static std::vector<ConvLayer> hand_layers() {  // model.py:331-392
 struct BufSpec {
   int level, cs, pad;
   int half = 0;   // W/2 wide (the pair-max buffer of a fused pool, ConvLaunch::hpool)
+  int out32 = 0;  // the fp32 copy of a net output in an fp16-storage arena (no bytes in an fp32 arena)
 };
 
 struct Op {
@@ -219,6 +220,9 @@ struct isl_net {
   int in_buf = 0;
   OutRef out0{}, out1{};
   int n_out = 2;
+  // ISL_ACT_FP16: per net output, its fp32 buffer in an fp16-storage arena (channels from 0)
+  // and the op that writes the output last (its epilogue stores both)
+  int out32_buf[2] = {-1, -1}, out_op[2] = {-1, -1};
   bool packed = false;
   bool packed_hi = false;      // the hi-only packs (ISL_PREC_FP16) match the current weights
   // plan
@@ -227,6 +231,7 @@ struct isl_net {
   // activation arenas by net input size (h, w), sized by frame capacity (plan())
   struct Arena {
     void* base = nullptr;
+    bool a16 = false;           // an fp16-storage arena (ISL_ACT_FP16): Act::esize 2 between the convs
     int n_cap = 0;
     std::vector<size_t> offs;   // buffer offsets for n_cap frames
     size_t bytes = 0;
@@ -294,6 +299,11 @@ struct isl_net {
   // ISL_PREC_*: products per MAC of the ISL_ALGO_X3 convs (isl_net_set_precision, env
   // ISLPOSE_PRECISION=fp32|fp16); stored without effect under the other algorithms
   int precision = ISL_PREC_FP32;
+  // ISL_ACT_*: storage of the activations between the ISL_PREC_FP16 convs (isl_net_set_act_storage,
+  // env ISLPOSE_ACT_STORAGE=fp32|fp16); stored without effect otherwise.  a16_active: the arena
+  // of the current plan is an fp16-storage one (plan() decides, per run, all or nothing)
+  int act_storage = ISL_ACT_FP32;
+  bool a16_active = false;
   int split_k = 1;             // isl_net_set_split_k: K-range mode (env ISLPOSE_X3_SPLITK=0|1|2)
   int* d_flag = nullptr;
   // range-guard trips: seen by the synchronous check (host count) and by the stream-ordered
@@ -1044,21 +1054,52 @@ static void drop_arena(isl_net* net, std::map<long long, isl_net::Arena>::iterat
   net->plans.erase(it);
 }
 
+// The buffers of an n-frame plan at net size h x w (no addresses yet).  a16: an fp16-storage arena
+// (ISL_ACT_FP16) -- every buffer between the convs holds fp16 (Act::esize 2), the net input and the
+// net outputs' own buffers stay fp32; those output buffers take no bytes in an fp32 arena.
+static std::vector<Act> layout_acts(const isl_net* net, int n, int h, int w, bool a16) {
+  const int lh[4] = {h, h / 2, h / 4, h / 8}, lw[4] = {w, w / 2, w / 4, w / 8};
+  std::vector<Act> act(net->bufs.size());
+  for (size_t i = 0; i < net->bufs.size(); ++i) {
+    const BufSpec& b = net->bufs[i];
+    Act& a = act[i];
+    a.n = b.out32 && !a16 ? 0 : n;
+    a.H = lh[b.level]; a.W = b.half ? lw[b.level] / 2 : lw[b.level]; a.pad = b.pad; a.cs = b.cs;
+    a.esize = a16 && !b.out32 && (int)i != net->in_buf ? 2 : 4;
+  }
+  return act;
+}
+
+static bool act16_plan_ok(const isl_net* net);
+
+// Whether an n-frame run at h x w stores its activations as fp16: the switch is on, it applies
+// (ISL_ALGO_X3 with ISL_PREC_FP16) and every conv of the run would take a kernel with an
+// fp16-storage form -- all or nothing, decided before the first launch with the predicates the
+// launches use (act16_plan_ok).
+static bool act16_for(isl_net* net, int n, int h, int w) {
+  if (net->act_storage != ISL_ACT_FP16 || net->algo != ISL_ALGO_X3 || net->precision != ISL_PREC_FP16) return false;
+  std::vector<Act> geo = layout_acts(net, n, h, w, true);
+  net->act.swap(geo);            // the predicates read the plan's geometry from net->act
+  const bool ok = act16_plan_ok(net);
+  net->act.swap(geo);
+  return ok;
+}
+
 static int plan(isl_net* net, int n, int h, int w, hipStream_t s) {
   if (n <= 0 || h < 8 || w < 8) return fail(ISL_E_ARG, "net input must be at least 8x8 with n >= 1");
-  const long long key = ((long long)h << 20) | w;
+  // arenas by (net size, storage)
+  const bool a16 = act16_for(net, n, h, w);
+  const long long key = ((long long)h << 20) | w | (a16 ? 1LL << 62 : 0);
   auto it = net->plans.find(key);
   if (it != net->plans.end() && it->second.n_cap < n) {
     drop_arena(net, it);
     it = net->plans.end();
   }
   if (it == net->plans.end()) {
-    const int lh0[4] = {h, h / 2, h / 4, h / 8}, lw0[4] = {w, w / 2, w / 4, w / 8};
     isl_net::Arena ar;
     ar.n_cap = n;
-    for (const BufSpec& b : net->bufs) {
-      Act a;
-      a.n = n; a.H = lh0[b.level]; a.W = b.half ? lw0[b.level] / 2 : lw0[b.level]; a.pad = b.pad; a.cs = b.cs;
+    ar.a16 = a16;
+    for (const Act& a : layout_acts(net, n, h, w, a16)) {
       ar.offs.push_back(ar.bytes);
       ar.bytes += (a.bytes() + 255) / 256 * 256;
     }
@@ -1081,15 +1122,10 @@ static int plan(isl_net* net, int n, int h, int w, hipStream_t s) {
   isl_net::Arena& ar = it->second;
   ar.last_use = ++net->plan_clock;
   net->cur = &ar;
+  net->a16_active = ar.a16;
   if (net->arena == ar.base && net->pn == n && net->ph == h && net->pw == w) return ISL_OK;
-  const int lh[4] = {h, h / 2, h / 4, h / 8}, lw[4] = {w, w / 2, w / 4, w / 8};
-  net->act.assign(net->bufs.size(), Act{});
-  for (size_t i = 0; i < net->bufs.size(); ++i) {
-    const BufSpec& b = net->bufs[i];
-    Act& a = net->act[i];
-    a.n = n; a.H = lh[b.level]; a.W = b.half ? lw[b.level] / 2 : lw[b.level]; a.pad = b.pad; a.cs = b.cs;
-    a.base = (float*)((char*)ar.base + ar.offs[i]);
-  }
+  net->act = layout_acts(net, n, h, w, ar.a16);
+  for (size_t i = 0; i < net->bufs.size(); ++i) net->act[i].base = (float*)((char*)ar.base + ar.offs[i]);
   net->arena = ar.base;
   net->pn = n; net->ph = h; net->pw = w;
   return ISL_OK;
@@ -1110,6 +1146,13 @@ static int default_algo() {
 static int default_precision() {
   const char* e = getenv("ISLPOSE_PRECISION");
   return e && std::string(e) == "fp16" ? ISL_PREC_FP16 : ISL_PREC_FP32;
+}
+
+// Activation storage of a net's ISL_PREC_FP16 convs (isl_net_set_act_storage);
+// ISLPOSE_ACT_STORAGE=fp32|fp16 sets the default at isl_net_create (unset or anything else: fp32).
+static int default_act_storage() {
+  const char* e = getenv("ISLPOSE_ACT_STORAGE");
+  return e && std::string(e) == "fp16" ? ISL_ACT_FP16 : ISL_ACT_FP32;
 }
 
 #ifdef ISLPOSE_DEV
@@ -1216,6 +1259,59 @@ static ConvLaunch basic_launch(const isl_net* net, const Op& op) {
   L.wx3 = c.d_wx3; L.wscale_inv = c.x3_inv; L.range_flag = net->d_flag;
   L.allow_split = net->split_k;
   return L;
+}
+
+// ISL_ACT_FP16 is all or nothing per run: whether every conv of a one-term run on the plan in
+// net->act (geometry only) would take a kernel with an fp16-storage form.  The walk makes the
+// choices of run_ops_eager in that mode (no fused pair, no conv1_1 -> conv1_2 launch, no Winograd
+// kernel) with the same predicates, up to the launch: the 3-channel kernel, or x3_act16_ok.  A conv
+// off the x3 kernels, a fold plan or K ranges across blocks (split-K, the wave-range kernel: the
+// latency-bound small grids) send the whole run to an fp32 arena.
+static bool act16_plan_ok(const isl_net* net) {
+  if (fold_enabled()) return false;
+#ifdef ISLPOSE_DEV
+  if (x3_wino_enabled()) return false;
+#endif
+  bool fused = false;
+  int vin_buf = -1;
+  const bool fuse_pools = fused_pool_enabled(), pool_input = fuse_pools && pool_input_enabled();
+  for (size_t k = 0; k < net->ops.size(); ++k) {
+    const Op& op = net->ops[k];
+    if (op.type == 1) {
+      if (fused && pool_input && pool_into_next_conv(net, k)) vin_buf = (int)k;
+      fused = false;
+      continue;
+    }
+    const ConvLayer& c = net->layers[op.layer];
+    ConvLaunch L = basic_launch(net, op);
+    if (!x3_fits(L)) return false;
+    if (vin_buf >= 0) {
+      const Act& hb = net->act[net->ops[vin_buf].hbuf];
+      ConvLaunch Lv = L;
+      Lv.in_cs = hb.cs; Lv.in_coff = 0; Lv.vin = 1;
+      if (x3_vin_ok(Lv) && !(c.d_wrgb && x3_rgb_fits(L))) L = Lv;
+      vin_buf = -1;
+    }
+    if (c.x3_wide) {
+      ConvLaunch Lw = L;
+      Lw.bco = 256;
+      if (x3_wide1(Lw)) L.bco = 256;
+    }
+    L.f16 = 1;
+    if (k + 1 < net->ops.size() && net->ops[k + 1].type == 1 && net->ops[k + 1].in == op.out && op.out_coff == 0 &&
+        net->ops[k + 1].C == c.cout && fuse_pools && x3_hpool_ok(L)) {
+      L.out_pad = 0; L.out_cs = net->act[net->ops[k + 1].hbuf].cs; L.out_coff = 0;
+      L.hpool = 1;
+      fused = true;
+    }
+    if (c.d_wrgb && x3_rgb_fits(L) && rgb_kernel_enabled() && !L.vin) {
+      if (op.out == net->in_buf) return false;
+      continue;
+    }
+    // (the net input is fp32 in every arena: only the 3-channel kernel reads it)
+    if (op.in == net->in_buf || !x3_act16_ok(L)) return false;
+  }
+  return true;
 }
 
 // Split-K fold plan of the current arena at its batch size (small grids, e.g. batch-1
@@ -1362,6 +1458,10 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
   // have no one-term form and run as their layers; the Winograd kernel is never chosen.
   const bool h16 = net->algo == ISL_ALGO_X3 && net->precision == ISL_PREC_FP16;
   if (h16 && !net->packed_hi) return fail(ISL_E_STATE, "fp16 precision: hi-only filters not uploaded");
+  // ISL_ACT_FP16: the arena of this plan holds fp16 between the convs (plan() found every conv
+  // covered); the launches below are those of the fp32-storage run, on the fp16-storage forms
+  const bool a16 = net->cur->a16;
+  if (a16 && !h16) return fail(ISL_E_STATE, "fp16 activation storage: the arena of this plan needs ISL_ALGO_X3 with ISL_PREC_FP16");
   const int f67 = net->algo == ISL_ALGO_X3 && !h16 ? fuse67_mode() : 0;
   size_t perm_op = (size_t)-1;   // the pair (perm_op, perm_op + 1) runs as its permuted two launches
   for (size_t k = 0; k < net->ops.size(); ++k) {
@@ -1525,6 +1625,15 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
         L.f16 = 1;
         L.wx3 = L.bco == 256 && c.x3_wide ? c.d_hx3w : c.d_hx3;
       }
+      if (a16) {
+        L.act16 = 1;
+        // the layer that writes a net output last also keeps the unrounded fp32 values
+        for (int o = 0; o < net->n_out; ++o)
+          if ((int)k == net->out_op[o]) {
+            const Act& ob = net->act[net->out32_buf[o]];
+            L.out32 = ob.base; L.out32_pad = ob.pad; L.out32_cs = ob.cs;
+          }
+      }
       // the next op pools this conv's output: write pair maxima to its half-width buffer
       if (k + 1 < net->ops.size() && net->ops[k + 1].type == 1 && net->ops[k + 1].in == op.out && op.out_coff == 0 &&
           net->ops[k + 1].C == c.cout && fuse_pools && x3_hpool_ok(L)) {
@@ -1590,6 +1699,7 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
       }
       net->op_variant[k] = x3_last_variant() | (L.fold_out ? X3V_FOLD_OUT : 0);
     } else {
+      if (a16) return fail(ISL_E_STATE, "fp16 activation storage: a conv off the x3 kernels");
       HIP_OK(launch_conv(L, s));
       mf = conv_mfma_flops(L);
     }
@@ -1621,7 +1731,7 @@ static const char* const kRunKeySwitches[] = {
     "ISLPOSE_X3_TILES",  "ISLPOSE_X3_UNION", "ISLPOSE_X3_HALF64",  "ISLPOSE_X3_WIDE7",   "ISLPOSE_X3_ACROSS",
     "ISLPOSE_X3_S8",     "ISLPOSE_X3_FUSE67", "ISLPOSE_X3_G2", "ISLPOSE_X3_PX64", "ISLPOSE_X3_HALFSMALL",
     "ISLPOSE_X3_WR",     "ISLPOSE_X3_WR_WN", "ISLPOSE_C12",        "ISLPOSE_X3_TAIL",    "ISLPOSE_X3_SMALL7",
-    "ISLPOSE_X3_W2",     "ISLPOSE_X3_S7W96",
+    "ISLPOSE_X3_W2",     "ISLPOSE_X3_S7W96", "ISLPOSE_A16_DMA",
 #ifdef ISLPOSE_DEV
     "ISLPOSE_X3_HALFCO", "ISLPOSE_X3_PPS2",  "ISLPOSE_X3_M16",     "ISLPOSE_X3_WINO",    "ISLPOSE_X3_ABL",
 #endif
@@ -1631,7 +1741,8 @@ static unsigned long long run_key(const isl_net* net) {
   unsigned long long h = 1469598103934665603ull;
   auto mix = [&](unsigned long long v) { h = (h ^ v) * 1099511628211ull; };
   mix((unsigned long long)net->pn);
-  mix((unsigned long long)net->split_k + 16 * (unsigned long long)net->algo + 256 * (unsigned long long)net->precision);
+  mix((unsigned long long)net->split_k + 16 * (unsigned long long)net->algo + 256 * (unsigned long long)net->precision +
+      4096 * (unsigned long long)(net->cur && net->cur->a16 ? 1 : 0));
   for (const char* name : kRunKeySwitches) {
     const char* v = getenv(name);
     for (const char* c = name; *c; ++c) mix((unsigned char)*c);
@@ -1742,10 +1853,21 @@ static int run_ops_graph(isl_net* net, hipStream_t s) {
   return launch(G);
 }
 
+// Net output `which` of the current plan: its slice of the stage buffers, or (an fp16-storage
+// arena) the fp32 buffer of its own that the last layer writing it also stores to
+static OutRef out_ref(const isl_net* net, int which) {
+  const OutRef& o = which == 0 ? net->out0 : net->out1;
+  if (net->cur && net->cur->a16) return OutRef{net->out32_buf[which], 0, o.C};
+  return o;
+}
+
 static int copy_outputs(isl_net* net, float* d_out0, float* d_out1, hipStream_t s) {
-  if (d_out0) HIP_OK(launch_unpack_nchw(net->act[net->out0.buf], net->out0.coff, net->out0.C, d_out0, s));
-  if (d_out1 && net->n_out > 1)
-    HIP_OK(launch_unpack_nchw(net->act[net->out1.buf], net->out1.coff, net->out1.C, d_out1, s));
+  const OutRef o0 = out_ref(net, 0);
+  if (d_out0) HIP_OK(launch_unpack_nchw(net->act[o0.buf], o0.coff, o0.C, d_out0, s));
+  if (d_out1 && net->n_out > 1) {
+    const OutRef o1 = out_ref(net, 1);
+    HIP_OK(launch_unpack_nchw(net->act[o1.buf], o1.coff, o1.C, d_out1, s));
+  }
   return ISL_OK;
 }
 
@@ -1754,8 +1876,9 @@ int net_device(const isl_net* net) { return net->device; }
 
 int net_low_res(isl_net* net, int which, MapSrc* m) {
   if (!net->arena) return fail(ISL_E_STATE, "no network output in the arena (run the net first)");
-  const OutRef& o = which == 0 ? net->out0 : net->out1;
+  const OutRef o = out_ref(net, which);
   const Act& a = net->act[o.buf];
+  if (a.esize != 4) return fail(ISL_E_STATE, "network output buffer is not fp32");
   const int Wp = a.W + 2 * a.pad;
   if (o.coff % 8) return fail(ISL_E_STATE, "network output slice not on a chunk");
   m->base = a.base + (size_t)(o.coff / 8) * a.chunk_elems() + ((size_t)a.pad * Wp + a.pad) * 8;
@@ -1819,6 +1942,7 @@ int isl_net_create(int kind, int device, isl_net** out) {
   net->device = device;
   net->algo = default_algo();
   net->precision = default_precision();
+  net->act_storage = default_act_storage();
   {
     // K-range mode (isl_net_set_split_k): 1 canonical ranges (default), 0 none, 2 latency
     const char* e = getenv("ISLPOSE_X3_SPLITK");
@@ -1836,6 +1960,15 @@ int isl_net_create(int kind, int device, isl_net** out) {
   else if (kind == ISL_COCO) build_coco(net);
   else build_hand(net);
   plan_fuse67(net);
+  // ISL_ACT_FP16: an fp32 buffer per net output (allocated in fp16-storage arenas only), and
+  // the last op that writes the output
+  for (int o = 0; o < net->n_out; ++o) {
+    const OutRef& r = o == 0 ? net->out0 : net->out1;
+    net->bufs.push_back({net->bufs[r.buf].level, round8(r.C), net->bufs[r.buf].pad, 0, 1});
+    net->out32_buf[o] = (int)net->bufs.size() - 1;
+    for (size_t k = 0; k < net->ops.size(); ++k)
+      if (net->ops[k].type == 0 && net->ops[k].out == r.buf && net->ops[k].out_coff == r.coff) net->out_op[o] = (int)k;
+  }
   *out = net;
   return ISL_OK;
 }
@@ -2130,6 +2263,20 @@ int isl_net_set_precision(isl_net* net, int precision) {
 
 int isl_net_get_precision(const isl_net* net) { return net ? net->precision : fail(ISL_E_ARG, "net is NULL"); }
 
+int isl_net_set_act_storage(isl_net* net, int storage) {
+  if (!net) return fail(ISL_E_ARG, "net is NULL");
+  if (storage != ISL_ACT_FP32 && storage != ISL_ACT_FP16) return fail(ISL_E_ARG, "unknown activation storage");
+  // (arenas are kept per storage and captured graphs keyed by it: a switch re-plans the next run)
+  net->act_storage = storage;
+  return ISL_OK;
+}
+
+int isl_net_get_act_storage(const isl_net* net) { return net ? net->act_storage : fail(ISL_E_ARG, "net is NULL"); }
+
+int isl_net_act_storage_active(const isl_net* net) {
+  return net ? (net->a16_active ? 1 : 0) : fail(ISL_E_ARG, "net is NULL");
+}
+
 int isl_lane_stream_create(int device, int priority_class, void** stream) {
   if (!stream) return fail(ISL_E_ARG, "stream is NULL");
   if (priority_class < -1 || priority_class > 1) return fail(ISL_E_ARG, "priority class must be -1, 0 or 1");
@@ -2234,6 +2381,18 @@ int isl_net_run(isl_net* net, float* d_out0, float* d_out1, void* stream) {
   int rc = prepare(net);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
+  // The input sits in the arena isl_net_preprocess* planned.  If the algorithm, precision or
+  // storage changed since (e.g. an ISL_ALGO_DIRECT recompute without a new preprocess), this run
+  // may need the size's other arena: plan it and carry the fp32 net input over, in stream order.
+  if (act16_for(net, net->pn, net->ph, net->pw) != net->cur->a16) {
+    const void* old_base = net->arena;
+    const Act old_in = net->act[net->in_buf];
+    if ((rc = plan(net, net->pn, net->ph, net->pw, s))) return rc;
+    bool alive = false;
+    for (auto& kv : net->plans) alive |= kv.second.base == old_base;
+    if (!alive) return fail(ISL_E_STATE, "isl_net_run: the arena holding the input was evicted; preprocess again");
+    HIP_OK(hipMemcpyAsync(net->act[net->in_buf].base, old_in.base, old_in.bytes(), hipMemcpyDeviceToDevice, s));
+  }
   if ((rc = run_ops(net, s))) return rc;
   return copy_outputs(net, d_out0, d_out1, s);
 }

@@ -48,10 +48,13 @@ class FrameResult:
 
 class BodyEstimator:
     def __init__(self, weights: dict = None, model_type: str = "body25", device: int = 0, scale_search=(0.5,),
-                 caps=None, net: "rt.Net" = None, precision: str = None):
+                 caps=None, net: "rt.Net" = None, precision: str = None, *, act_storage: str = None):
         """precision: 'fp32' or 'fp16' (rt.Net.set_precision) for the net, or None to keep
-        the net's own -- fp32 unless ISLPOSE_PRECISION=fp16 was set when it was created."""
+        the net's own -- fp32 unless ISLPOSE_PRECISION=fp16 was set when it was created.
+        act_storage: 'fp32' or 'fp16' (rt.Net.set_act_storage: fp16 activation buffers under
+        precision 'fp16', the same results), or None to keep the net's own."""
         rt.check_precision(precision)
+        rt.check_act_storage(act_storage)
         self.kind = KINDS[model_type]
         self.model_type = model_type
         self.device = device
@@ -63,6 +66,8 @@ class BodyEstimator:
         assert net.kind == self.kind
         if precision is not None:
             net.set_precision(precision)
+        if act_storage is not None:
+            net.set_act_storage(act_storage)
         self.net = net
         self.njoint, self.npaf = NJOINT[self.kind], NPAF[self.kind]
 

@@ -24,10 +24,14 @@ CROP_CHUNK = 64     # hand crops per batched pass of estimate_crops
 
 class HandEstimator:
     def __init__(self, weights: dict = None, device: int = 0, scale_search=HAND_SCALES, net: "rt.Net" = None,
-                 precision: str = None):
+                 precision: str = None, *, act_storage: str = None):
         """precision: 'fp32' or 'fp16' (rt.Net.set_precision) for the net, or None to keep
-        the net's own -- fp32 unless ISLPOSE_PRECISION=fp16 was set when it was created."""
+        the net's own -- fp32 unless ISLPOSE_PRECISION=fp16 was set when it was created.
+        act_storage: 'fp32' or 'fp16' (rt.Net.set_act_storage: fp16 activation buffers under
+        precision 'fp16', the same results; the small scales keep fp32 buffers), or None to keep
+        the net's own."""
         rt.check_precision(precision)
+        rt.check_act_storage(act_storage)
         self.device = device
         self.scale_search = tuple(scale_search)
         if net is None:
@@ -36,6 +40,8 @@ class HandEstimator:
         assert net.kind == rt.ISL_HAND
         if precision is not None:
             net.set_precision(precision)
+        if act_storage is not None:
+            net.set_act_storage(act_storage)
         self.net = net
 
     def run_scales(self, crops):

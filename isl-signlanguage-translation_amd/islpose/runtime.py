@@ -20,6 +20,10 @@ ALGOS = {"x3": ISL_ALGO_X3, "wino": ISL_ALGO_WINO, "direct": ISL_ALGO_DIRECT}
 # fp16 product per multiply-add (opt-in; ~2e-3 of the maps' maximum in error)
 ISL_PREC_FP32, ISL_PREC_FP16 = 0, 1
 PRECISIONS = {"fp32": ISL_PREC_FP32, "fp16": ISL_PREC_FP16}
+# storage of the activations between the fp16-precision convs (isl_act_storage): fp32 (default) or
+# fp16 (opt-in; the same bits as fp32 storage, half the activation bytes)
+ISL_ACT_FP32, ISL_ACT_FP16 = 0, 1
+ACT_STORAGES = {"fp32": ISL_ACT_FP32, "fp16": ISL_ACT_FP16}
 
 
 def check_precision(name):
@@ -27,6 +31,14 @@ def check_precision(name):
     if name is not None and name not in PRECISIONS:
         raise ValueError("unknown precision %r (expected one of %s)" % (name, ", ".join(PRECISIONS)))
     return name
+
+
+def check_act_storage(name):
+    """`name` if it is a key of ACT_STORAGES (or None: keep the net's own), else ValueError."""
+    if name is not None and name not in ACT_STORAGES:
+        raise ValueError("unknown activation storage %r (expected one of %s)" % (name, ", ".join(ACT_STORAGES)))
+    return name
+
 
 LIB_PATH = os.environ.get("ISLPOSE_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "libislpose.so"))
 
@@ -38,7 +50,8 @@ EXPORTS = ["isl_abi_version", "isl_last_error", "isl_net_create", "isl_net_destr
            "isl_sign_param_count", "isl_sign_classify", "isl_net_set_split_k", "isl_net_arena_info",
            "isl_debug_np_sum", "isl_hand_post_crops", "isl_net_check_async", "isl_net_range_info",
            "isl_net_op_info", "isl_net_set_graph", "isl_lane_stream_create", "isl_lane_stream_destroy",
-           "isl_net_set_precision", "isl_net_get_precision"]
+           "isl_net_set_precision", "isl_net_get_precision", "isl_net_set_act_storage",
+           "isl_net_get_act_storage", "isl_net_act_storage_active"]
 
 
 class IslCaps(ctypes.Structure):
@@ -95,6 +108,9 @@ def lib():
     L.isl_net_get_algo.argtypes = [vp]
     L.isl_net_set_precision.argtypes = [vp, i32]
     L.isl_net_get_precision.argtypes = [vp]
+    L.isl_net_set_act_storage.argtypes = [vp, i32]
+    L.isl_net_get_act_storage.argtypes = [vp]
+    L.isl_net_act_storage_active.argtypes = [vp]
     L.isl_net_check.argtypes = [vp, i32]
     L.isl_net_check_async.argtypes = [vp, vp, vp]
     L.isl_net_range_info.argtypes = [vp, ctypes.POINTER(i64)]
@@ -251,7 +267,8 @@ def ptr(t) -> ctypes.c_void_p:
 def decode_variant(code: int) -> dict:
     """isl_net_op_info's variant code -> dict(var=VAR bits, bpx, bco, ks, rgb, pool_fused, ...):
     wave_ranges (conv_x3_wr, VAR 8), c12 (conv1_1 -> conv1_2 in one launch, 4), wino2 (the
-    split-fp16 Winograd kernel wino_f16, 64), f16 (one-term fp16 products, precision 'fp16', 2)."""
+    split-fp16 Winograd kernel wino_f16, 64), f16 (one-term fp16 products, precision 'fp16', 2),
+    act16 (the launch reads or writes fp16 activations, act_storage 'fp16', 1)."""
     if code == -1:
         return {"pool_fused": True}
     if code == -2:
@@ -266,7 +283,7 @@ def decode_variant(code: int) -> dict:
             "pairs2": bool(code & 4096), "vin": bool(code & 32768), "sib": bool(code & 65536),
             "fold": bool(code & 8192), "m16": bool(code & 131072), "fold_out": bool(code & (1 << 19)),
             "wave_ranges": bool(code & 8), "c12": bool(code & 4), "wino2": bool(code & 64),
-            "f16": bool(code & 2)}
+            "f16": bool(code & 2), "act16": bool(code & 1)}
 
 
 class Net:
@@ -372,6 +389,39 @@ class Net:
             finally:
                 self.set_precision(prev)
         return scope()
+
+    # -- storage of the activations between the fp16-precision convs ------------------
+    @property
+    def act_storage(self) -> str:
+        a = lib().isl_net_get_act_storage(self.h)
+        return {v: k for k, v in ACT_STORAGES.items()}[a]
+
+    def set_act_storage(self, name: str):
+        """'fp32' (default, or the env ISLPOSE_ACT_STORAGE at creation) or 'fp16': under the 'x3'
+        algorithm with precision 'fp16' the arena buffers between the convs hold fp16 -- the
+        roundings the kernels would have made anyway, so the outputs are the same bits -- at
+        half the activation bytes.  Stored without effect otherwise; a run with a conv that has
+        no fp16-storage kernel keeps fp32 buffers as a whole (act_storage_active).  Unknown names
+        raise ValueError."""
+        check(lib().isl_net_set_act_storage(self.h, ACT_STORAGES[check_act_storage(name)]), "isl_net_set_act_storage")
+
+    def act_storage_scope(self, name: str):
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            prev = self.act_storage
+            self.set_act_storage(name)
+            try:
+                yield
+            finally:
+                self.set_act_storage(prev)
+        return scope()
+
+    @property
+    def act_storage_active(self) -> bool:
+        """Whether the last run stored its activations as fp16 (isl_net_act_storage_active)."""
+        return lib().isl_net_act_storage_active(self.h) == 1
 
     def set_split_k(self, mode):
         """K-range mode of the x3 convs (isl_net_set_split_k): 1 canonical ranges (default,

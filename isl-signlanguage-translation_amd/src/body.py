@@ -12,6 +12,10 @@ convolutions: 'fp32', or 'fp16' (one fp16 product per multiply-add, faster, ~2e-
 maximum in error); the default None is the library's own, fp32 unless ISLPOSE_PRECISION=fp16
 is set.  An unknown value raises ValueError.  The CPU path is fp32 whatever
 is given.
+``act_storage`` (keyword only, not in the reference): 'fp32' or 'fp16' for the buffers between the
+GPU convolutions of precision 'fp16' (fp16: half the activation memory, the same results); None
+keeps the library's own (fp32 unless ISLPOSE_ACT_STORAGE=fp16 is set); an unknown value raises
+ValueError; no effect on the CPU path or under precision 'fp32'.
 ``estimate_batch(frames)`` processes a batch of frames in one pass.
 """
 from __future__ import annotations
@@ -28,8 +32,9 @@ from .model import bodypose_25_model, bodypose_model
 
 
 class Body(object):
-    def __init__(self, model_path, model_type="coco", *, precision=None):
+    def __init__(self, model_path, model_type="coco", *, precision=None, act_storage=None):
         rt.check_precision(precision)
+        rt.check_act_storage(act_storage)
         if model_type == "coco":
             self.model, self.njoint, self.npaf = bodypose_model(), 19, 38
         elif model_type == "body25":
@@ -46,6 +51,8 @@ class Body(object):
         self.model.eval()
         self.precision = precision
         self.model.set_precision(precision)
+        self.act_storage = act_storage
+        self.model.set_act_storage(act_storage)
         self.scale_search = [0.5]          # body.py:41
         self._est = None
 

@@ -6,6 +6,9 @@ maximum -- all on the GPU (on a host without a visible HIP device, on the CPU: i
 ``precision`` (keyword only, not in the reference): 'fp32' or 'fp16' for the GPU convolutions;
 the default None is the library's own (fp32 unless ISLPOSE_PRECISION=fp16 is set); an unknown
 value raises ValueError; no effect on the CPU path, which is fp32.
+``act_storage`` (keyword only, not in the reference): 'fp32' or 'fp16' for the buffers between the
+GPU convolutions of precision 'fp16' (the same results at half the activation memory); None keeps
+the library's own; an unknown value raises ValueError.
 """
 from __future__ import annotations
 
@@ -21,8 +24,9 @@ from .model import handpose_model
 
 
 class Hand(object):
-    def __init__(self, model_path, *, precision=None):
+    def __init__(self, model_path, *, precision=None, act_storage=None):
         rt.check_precision(precision)
+        rt.check_act_storage(act_storage)
         self.model = handpose_model()
         if torch.cuda.is_available():
             self.model = self.model.cuda()
@@ -32,6 +36,8 @@ class Hand(object):
         self.model.eval()
         self.precision = precision
         self.model.set_precision(precision)
+        self.act_storage = act_storage
+        self.model.set_act_storage(act_storage)
         self._est = None
 
     def estimator(self) -> HandEstimator:

@@ -55,6 +55,7 @@ class _NativeNet(nn.Module):
         object.__setattr__(self, "_native_net", None)
         object.__setattr__(self, "_native_key", None)
         object.__setattr__(self, "_native_precision", None)
+        object.__setattr__(self, "_native_act_storage", None)
 
     def set_precision(self, name):
         """Precision of this module's native net (rt.Net.set_precision): 'fp32', 'fp16', or None
@@ -65,6 +66,21 @@ class _NativeNet(nn.Module):
         object.__setattr__(self, "_native_precision", name)
         if name is not None and self._native_net is not None:
             self._native_net.set_precision(name)
+
+    def set_act_storage(self, name):
+        """Activation storage of this module's native net (rt.Net.set_act_storage): 'fp32', 'fp16',
+        or None for the library default (fp32 unless ISLPOSE_ACT_STORAGE=fp16).  Kept on the module
+        until the native net exists, like set_precision.  It changes no result (the fp16 buffers
+        hold the roundings the fp16-precision kernels make anyway), only the activation memory."""
+        rt.check_act_storage(name)
+        object.__setattr__(self, "_native_act_storage", name)
+        if name is not None and self._native_net is not None:
+            self._native_net.set_act_storage(name)
+
+    @property
+    def act_storage(self):
+        """The native net's activation storage once it exists, else what set_act_storage stored."""
+        return self._native_net.act_storage if self._native_net is not None else self._native_act_storage
 
     @property
     def precision(self):
@@ -97,6 +113,8 @@ class _NativeNet(nn.Module):
             net = rt.Net(self.KIND, device_index)
             if self._native_precision is not None:
                 net.set_precision(self._native_precision)
+            if self._native_act_storage is not None:
+                net.set_act_storage(self._native_act_storage)
             object.__setattr__(self, "_native_net", net)
             object.__setattr__(self, "_native_key", None)
         key = self._param_key()

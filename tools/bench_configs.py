@@ -305,13 +305,20 @@ def main():
                     help="precision of the x3 convs of every net (rt.Net.set_precision): fp32 = three fp16 "
                          "products per multiply-add (fp32-accurate, the default), fp16 = one (faster, ~2e-3 "
                          "of the maps' maximum in error); default: the library's (env ISLPOSE_PRECISION)")
+    ap.add_argument("--act-storage", choices=["fp32", "fp16"], default=None,
+                    help="storage of the activations between the fp16-precision convs of every net "
+                         "(rt.Net.set_act_storage): fp16 halves the activation buffers at the same bits; "
+                         "default: the library's (env ISLPOSE_ACT_STORAGE)")
     a = ap.parse_args()
     if a.precision:
         os.environ["ISLPOSE_PRECISION"] = a.precision   # read by every net at its creation
+    if a.act_storage:
+        os.environ["ISLPOSE_ACT_STORAGE"] = a.act_storage
     for name, fn in (("c3", c3), ("c4", c4), ("c5", c5), ("c6", c6), ("frame", frame)):
         if a.config in (name, "all"):
             res = fn(a)
             res["precision"] = os.environ.get("ISLPOSE_PRECISION", "fp32")
+            res["act_storage"] = os.environ.get("ISLPOSE_ACT_STORAGE", "fp32")
             print(json.dumps(res), flush=True)
 
 
