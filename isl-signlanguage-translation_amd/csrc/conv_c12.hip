@@ -19,6 +19,15 @@
 // Channel halves: conv1_1's 64 outputs are staged 32 at a time (chunk pairs 0-1, then 2-3) so
 // the halo buffer is 45 KB and two blocks fit a CU; conv1_2 walks its pairs in order across the
 // two halves, so its K order is unchanged.
+//
+// F16 (ISL_PREC_FP16): the one-term form.  conv1_1 from the hi-only rgb pack (one MFMA per K step
+// on the inputs' fp16 roundings), its activated value written to the halo buffer as its single
+// fp16 rounding (RNE, no lo plane: the buffer and the weight slabs are half the bytes), conv1_2
+// from the hi-only 64-channel pack, one MFMA per tap.  Same K packing and order, epilogues, range
+// checks (on the fp32 values) and pool maxima: the bits of conv_x3_rgb<.., true> followed by the
+// one-term 64-channel generic loop and the pool.  O16 (ISL_ACT_FP16, with F16): the pooled map /
+// the pair-max buffer is an fp16 buffer and takes RNE(v) (x3_store4h's layout and masks); the net
+// input stays fp32.
 #include <algorithm>
 
 #include "internal.h"
@@ -41,22 +50,23 @@ constexpr int HG = (HPX + 31) / 32;             // 11 groups of 32 halo pixels (
 constexpr int HPS = HG * 32;                    // halo plane stride in the LDS buffer (352)
 constexpr int NT = 512;                         // 8 waves
 constexpr int WSL = 3 * 2 * 2 * 64;             // conv1_2 weight slab of one (pair, ky) step, 16-B units
+constexpr int WSLH = 3 * 2 * 64;                // ... of the hi-only pack (F16): [kx][h][64]
 
 struct C12Args {
   const float* in;                              // [n][1 chunk][H + 2 p][W + 2 p][8], channels 0-2
   long long in_fs;
   int in_pad;
-  const f16x8* w1;                              // pack_x3_rgb: [kk][hi|lo][h][64]
+  const f16x8* w1;                              // pack_x3_rgb: [kk][hi|lo][h][64] (F16: hi-only, [kk][h][64])
   const float* b1;
   const float* sl1;
   float s1_inv;
   int act1;
-  const f16x8* w2;                              // pack_x3 (64-channel tile): [pair][ky][kx][hi|lo][h][64]
+  const f16x8* w2;                              // pack_x3 (64-channel tile): [pair][ky][kx][hi|lo][h][64] (F16: no [hi|lo])
   const float* b2;
   const float* sl2;
   float s2_inv;
   int act2;
-  float* out;                                   // pool2: the pooled buffer [n][8 chunks][H/2 + 2 op][W/2 + 2 op][8];
+  float* out;                                   // (O16: fp16 elements) pool2: the pooled buffer [n][8 chunks][H/2 + 2 op][W/2 + 2 op][8];
   long long out_fs, out_chs;                    // else the pair-max buffer [n][8 chunks][H][W / 2][8]
   int pool2, out_pad, out_wp;                   // out_wp: padded pooled width W/2 + 2 out_pad
   int H, W, tiles_x, tiles_y, nblocks;
@@ -88,10 +98,16 @@ __device__ __forceinline__ float act_f(float v, int act, float slope) {
   return v;
 }
 
-template <bool RR>
+// the hi halves alone of 4 values (F16): the same RNE conversions, no residual
+__device__ __forceinline__ f16x4 hi4(const f32x4& a) { return __builtin_convertvector(a, f16x4); }
+
+template <bool RR, bool F16 = false, bool O16 = false>
 __global__ void __launch_bounds__(NT, 4) conv_x3_c12(C12Args a) {
-  __shared__ f16x8 s_x[2][4][HPS];              // conv1_1 output half: [hi|lo][chunk of the half][halo px]
-  __shared__ f16x8 s_w[2][WSL];                 // conv1_2 weight slabs, double-buffered
+  static_assert(!O16 || F16, "fp16 activation storage: the one-term kernel");
+  constexpr int NH = F16 ? 1 : 2;               // operand planes
+  constexpr int WSLK = F16 ? WSLH : WSL;
+  __shared__ f16x8 s_x[NH][4][HPS];             // conv1_1 output half: [hi|lo][chunk of the half][halo px]
+  __shared__ f16x8 s_w[2][WSLK];                // conv1_2 weight slabs, double-buffered
   __shared__ float s_p[256];                    // b1, b2, slopes1, slopes2
   __shared__ f32x4 s_in[TH + 4][TW + 4];        // the tile's input rows y0-2 .. y0+TH+1 (channels 0-3)
   const int tid = threadIdx.x, lane = tid & 63;
@@ -119,13 +135,21 @@ __global__ void __launch_bounds__(NT, 4) conv_x3_c12(C12Args a) {
   // an LDS-DMA in flight)
   f16x8 wreg[2];
   auto load_w = [&](int st) __attribute__((always_inline)) {
-    const f16x8* src = a.w2 + (size_t)st * WSL;
-    wreg[0] = src[tid];
-    if (tid < WSL - NT) wreg[1] = src[NT + tid];
+    const f16x8* src = a.w2 + (size_t)st * WSLK;
+    if constexpr (F16) {                        // 384 units: one per thread of the first 6 waves
+      if (tid < WSLH) wreg[0] = src[tid];
+    } else {
+      wreg[0] = src[tid];
+      if (tid < WSL - NT) wreg[1] = src[NT + tid];
+    }
   };
   auto store_w = [&](int b) __attribute__((always_inline)) {
-    s_w[b][tid] = wreg[0];
-    if (tid < WSL - NT) s_w[b][NT + tid] = wreg[1];
+    if constexpr (F16) {
+      if (tid < WSLH) s_w[b][tid] = wreg[0];
+    } else {
+      s_w[b][tid] = wreg[0];
+      if (tid < WSL - NT) s_w[b][NT + tid] = wreg[1];
+    }
   };
   load_w(0);
   store_w(0);
@@ -172,6 +196,12 @@ __global__ void __launch_bounds__(NT, 4) conv_x3_c12(C12Args a) {
           if (j < 4) v0[j] = v;
           else v1[j - 4] = v;
         }
+        if constexpr (F16) {
+          const f16x4 h0 = hi4(v0), h1 = hi4(v1);
+          const f16x8 Bh = f16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+          const f16x8 A0 = a.w1[(kk * 2 + h) * 64 + 32 * hf + l32];
+          acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(A0, Bh, acc1, 0, 0, 0);
+        } else {
         f16x4 h0, l0, h1, l1;
         split4(v0, h0, l0);
         split4(v1, h1, l1);
@@ -182,6 +212,7 @@ __global__ void __launch_bounds__(NT, 4) conv_x3_c12(C12Args a) {
         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(A0, Bh, acc1, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(A0, Bl, acc1, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(A1, Bh, acc1, 0, 0, 0);
+        }
       }
       // register r: channel 32 hf + (r & 3) + 8 (r >> 2) + 4 h of halo pixel hp; registers
       // 4c .. 4c + 3 are elements 4h .. 4h + 3 of chunk c of the half
@@ -196,10 +227,14 @@ __global__ void __launch_bounds__(NT, 4) conv_x3_c12(C12Args a) {
           bad |= inimg && !(__builtin_fabsf(t) < 65504.f);
           v[e] = inimg ? t : 0.f;
         }
+        if constexpr (F16) {
+          *(f16x4*)((_Float16*)&s_x[0][c][hp] + 4 * h) = hi4(v);
+        } else {
         f16x4 hi, lo;
         split4(v, hi, lo);
         *(f16x4*)((_Float16*)&s_x[0][c][hp] + 4 * h) = hi;
-        *(f16x4*)((_Float16*)&s_x[1][c][hp] + 4 * h) = lo;
+        *(f16x4*)((_Float16*)&s_x[NH - 1][c][hp] + 4 * h) = lo;
+        }
       }
     }
     __syncthreads();
@@ -212,18 +247,20 @@ __global__ void __launch_bounds__(NT, 4) conv_x3_c12(C12Args a) {
       const f16x8* sx = &s_x[0][2 * pp + h][(wave + ky) * HWD + l32];
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
-        f16x8 A[2][2], B[2];
+        f16x8 A[2][NH], B[NH];
 #pragma unroll
-        for (int hl = 0; hl < 2; ++hl) {
+        for (int hl = 0; hl < NH; ++hl) {
 #pragma unroll
-          for (int wm = 0; wm < 2; ++wm) A[wm][hl] = sw[(kx * 2 + hl) * 2 * 64 + wm * 32];
+          for (int wm = 0; wm < 2; ++wm) A[wm][hl] = sw[(kx * NH + hl) * 2 * 64 + wm * 32];
           B[hl] = sx[hl * 4 * HPS + kx];
         }
 #pragma unroll
         for (int wm = 0; wm < 2; ++wm) {
           acc2[wm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][0], B[0], acc2[wm], 0, 0, 0);
-          acc2[wm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][0], B[1], acc2[wm], 0, 0, 0);
-          acc2[wm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][1], B[0], acc2[wm], 0, 0, 0);
+          if constexpr (!F16) {
+            acc2[wm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][0], B[NH - 1], acc2[wm], 0, 0, 0);
+            acc2[wm] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[wm][NH - 1], B[0], acc2[wm], 0, 0, 0);
+          }
         }
       }
       if (st + 1 < 12) store_w(b ^ 1);   // buffer b ^ 1 was last read in the previous step
@@ -237,7 +274,9 @@ __global__ void __launch_bounds__(NT, 4) conv_x3_c12(C12Args a) {
   // in its staging).  max is exact in any order: the bits of maxpool2 / vpool2.
   const int y = y0 + wave, x = x0 + l32;
   const bool ok = y < a.H && x < a.W;
-  float* out_f = a.out + (size_t)n * a.out_fs;
+  // (O16: an fp16 buffer addressed in elements from out_f's address)
+  float* out_f = O16 ? (float*)((_Float16*)a.out + (size_t)n * a.out_fs) : a.out + (size_t)n * a.out_fs;
+  // (O16 stores: RNE of four channels, 8 B, at the same element offsets -- x3_store4h's layout)
   f32x4 pv[2][4];
 #pragma unroll
   for (int wm = 0; wm < 2; ++wm)
@@ -263,8 +302,13 @@ __global__ void __launch_bounds__(NT, 4) conv_x3_c12(C12Args a) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int co = wm * 32 + 8 * q + 4 * h;
+        if constexpr (O16) {
+          if (ok && !(x & 1))
+            *(f16x4*)((_Float16*)out_f + (size_t)(co >> 3) * a.out_chs + ((size_t)y * (a.W / 2) + (x >> 1)) * 8 + (co & 7)) = hi4(pv[wm][q]);
+        } else {
         if (ok && !(x & 1))
           *(f32x4*)(out_f + (size_t)(co >> 3) * a.out_chs + ((size_t)y * (a.W / 2) + (x >> 1)) * 8 + (co & 7)) = pv[wm][q];
+        }
       }
   } else {
     // the K loop ended on a barrier: s_x is free.  Slot (row pair, wm, q, h, even lane / 2).
@@ -279,7 +323,7 @@ __global__ void __launch_bounds__(NT, 4) conv_x3_c12(C12Args a) {
     }
     __syncthreads();
     if (!(wave & 1) && ok && y + 1 < a.H && !(x & 1)) {
-      float* op = out_f + ((size_t)((y >> 1) + a.out_pad) * a.out_wp + (x >> 1) + a.out_pad) * 8;
+      float* op = out_f + ((size_t)((y >> 1) + a.out_pad) * a.out_wp + (x >> 1) + a.out_pad) * (O16 ? 4 : 8);
 #pragma unroll
       for (int wm = 0; wm < 2; ++wm)
 #pragma unroll
@@ -289,7 +333,8 @@ __global__ void __launch_bounds__(NT, 4) conv_x3_c12(C12Args a) {
           f32x4 v = pv[wm][q];
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], u[e]);
-          *(f32x4*)(op + (size_t)(co >> 3) * a.out_chs + (co & 7)) = v;
+          if constexpr (O16) *(f16x4*)((_Float16*)op + (size_t)(co >> 3) * a.out_chs + (co & 7)) = hi4(v);
+          else *(f32x4*)(op + (size_t)(co >> 3) * a.out_chs + (co & 7)) = v;
         }
     }
   }
@@ -304,7 +349,8 @@ bool x3_c12_fits(const ConvLaunch& l1, const ConvLaunch& l2) {
          l2.ks == 3 && l2.cin_chunks == 8 && l2.cout == 64 && l2.bco == 64 && (l2.hpool == 1 || l2.hpool == 2) &&
          !(l2.W & 1) && l1.H == l2.H && l1.W == l2.W && l1.n == l2.n && l2.out_coff == 0 &&
          (l2.hpool == 2 ? l2.out_pad >= 0 : l2.out_pad == 0) && (l2.out_cs & 7) == 0 && l2.out_cs >= 64 && l1.wx3 &&
-         l2.wx3 && l1.range_flag;
+         l2.wx3 && l1.range_flag && l1.f16 == l2.f16 && l1.act16 == l2.act16 && (!l2.act16 || l2.f16) && !l1.out32 &&
+         !l2.out32;
 }
 
 hipError_t launch_conv_x3_c12(const ConvLaunch& l1, const ConvLaunch& l2, hipStream_t s) {
@@ -334,14 +380,23 @@ hipError_t launch_conv_x3_c12(const ConvLaunch& l1, const ConvLaunch& l2, hipStr
   const long long nb = (long long)l1.n * a.tiles_x * a.tiles_y;
   if (nb <= 0 || nb > 0x7fffffff) { set_error("conv_x3_c12: bad grid"); return hipErrorInvalidValue; }
   a.nblocks = (int)nb;
-  if (a.act1 == ACT_RELU && a.act2 == ACT_RELU) hipLaunchKernelGGL(conv_x3_c12<true>, dim3(a.nblocks), dim3(NT), 0, s, a);
+  const bool rr = a.act1 == ACT_RELU && a.act2 == ACT_RELU;
+  // (the one-term packs are l1.wx3 = pack_hi_only of the rgb pack, l2.wx3 = of the 64-channel pack;
+  // O16: l2.out is an fp16 buffer, the element strides are the same)
+  if (l2.act16) {
+    if (rr) hipLaunchKernelGGL((conv_x3_c12<true, true, true>), dim3(a.nblocks), dim3(NT), 0, s, a);
+    else hipLaunchKernelGGL((conv_x3_c12<false, true, true>), dim3(a.nblocks), dim3(NT), 0, s, a);
+  } else if (l2.f16) {
+    if (rr) hipLaunchKernelGGL((conv_x3_c12<true, true>), dim3(a.nblocks), dim3(NT), 0, s, a);
+    else hipLaunchKernelGGL((conv_x3_c12<false, true>), dim3(a.nblocks), dim3(NT), 0, s, a);
+  } else if (rr) hipLaunchKernelGGL(conv_x3_c12<true>, dim3(a.nblocks), dim3(NT), 0, s, a);
   else hipLaunchKernelGGL(conv_x3_c12<false>, dim3(a.nblocks), dim3(NT), 0, s, a);
   return hipGetLastError();
 }
 
 double conv_x3_c12_mfma_flops(const ConvLaunch& l1) {
   const double tiles = (double)l1.n * ((l1.W + TW - 1) / TW) * ((l1.H + TH - 1) / TH);
-  return tiles * 3.0 * 2.0 * (64.0 * 32.0 * HPS + 64.0 * 64.0 * 9.0 * TH * TW);
+  return tiles * (l1.f16 ? 1.0 : 3.0) * 2.0 * (64.0 * 32.0 * HPS + 64.0 * 64.0 * 9.0 * TH * TW);
 }
 
 }  // namespace isl

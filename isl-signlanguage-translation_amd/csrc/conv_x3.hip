@@ -45,11 +45,13 @@
 //         pooled-input form takes packed fp16 row-pair maxima) and the epilogue stores RNE(v), 8 B per
 //         4 channels, after the range check on the fp32 value; a layer writing a net output also stores
 //         the fp32 values (X3Args::out32).  Same tiles, K order and MFMA operands: the same bits as 2
-//         alone.  Combines with every bit 2 does but 2048 (and 8192);
+//         alone.  Combines with every bit 2 does but 2048 (and 8192); with 16 the fused
+//         epilogue stores RNE(v) of Mconv7's value (and the fp32 copy of a net output);
 //   2     one-term fp16 products (isl_net_set_precision ISL_PREC_FP16, opt-in): x*w ~= x_hi*w_hi alone,
 //         one MFMA per tap; every layout below loses its [hi|lo] dimension (hi-only weight slabs,
 //         inputs rounded once at staging), everything else -- tiles, K order, ranges, epilogue and
-//         range check -- is the variant's; combines with every bit but 16 and 131072;
+//         range check -- is the variant's; combines with every bit but 131072 (with 16: the fused
+//         epilogue rounds Mconv6's value once and runs one MFMA per K block on the hi-only pack_x3_f7);
 //   512   row union (3x3 on 512-pixel tiles): the three kernel rows of a chunk pair
 //         are staged once as one run, a third per ky step, by loader waves, while
 //         DMA waves stream the weights (role split, see the union loop);
@@ -353,7 +355,7 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
   // VAR 1: fp16 activation storage (x3_ld8 / x3_op8 / x3_store4h) -- in and out are fp16 buffers
   constexpr bool A16 = (VAR & X3V_A16) != 0;
   static_assert(!A16 || F16, "fp16 activation storage: the one-term kernels");
-  static_assert(!A16 || !(VAR & (16 | 2048 | 8192 | 16384 | 131072)), "fp16 activation storage: no split-K / fold / fused pair form");
+  static_assert(!A16 || !(VAR & (2048 | 8192 | 16384 | 131072)), "fp16 activation storage: no split-K / fold form");
   constexpr int WSLAB1 = KS * NH * 2 * BCO;      // one pair: [kx][hi|lo][h][BCO]
   constexpr int WSLAB = PPS * WSLAB1;            // 16-byte units per step
   constexpr int SEGP = SEGMAX + 1;               // + one dummy slot idle staging items write to
@@ -409,7 +411,6 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
   static_assert(!(FOLD && (VIN || UNION || M16 || KS > 3 || PPS > 1)), "fold: the generic loop of 1x1 / 3x3 layers");
   static_assert(!(UNION && (RANGED || SPLIT)), "K ranges run on the generic loop");
   static_assert(PPS == 1 || !(UNION || M16 || HALFCO || DEEP || FOLD || VIN), "two pairs per step: generic loop");
-  static_assert(!F16 || !(VAR & 16), "one-term products: the fused 1x1 pair is not built (the plan runs it unfused)");
   static_assert(!G2 || (RANGED && !SPLIT && !UNION && !M16 && !SIB && !DEEP && !FOLD && !VIN && !HALFCO && PPS == 1 &&
                         !FUSE67 && !STAMP),
                 "two K groups: in-block K ranges on the plain generic loop");
@@ -1333,7 +1334,8 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
     const float* bias7 = eb + 2 * BCO;
     const float* slope7 = eb + 2 * BCO + 64;
     const int Wo = a.W + 2 * a.out_pad;
-    float* out_f = a.out + (size_t)n * a.out_fs;
+    // (A16: Mconv7's output is an fp16 buffer addressed in elements from out_f's address)
+    float* out_f = A16 ? (float*)((_Float16*)a.out + (size_t)n * a.out_fs) : a.out + (size_t)n * a.out_fs;
 #pragma unroll
     for (int wn = 0; wn < WN; ++wn) {
       // Mconv6's epilogue (x 2^-s, bias, activation, range check) and the split: register r
@@ -1341,7 +1343,9 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
       // lane half h are the K = 16 B fragment of rows {16 kq + 4 h + 8 (j >> 2) + (j & 3)};
       // Mconv7's filters are packed in that K order (pack_x3_f7): no value leaves its lane
       const bool live = m0 + (wave_n * WN + wn) * 32 + l32 <= mlast;
-      f16x8 Bh[WM][2], Bl[WM][2];
+      // (F16: the activated value's single fp16 rounding, no Bl -- what the one-term Mconv7 of the
+      // two-launch form makes of it at staging, or reads back from an fp16 buffer)
+      f16x8 Bh[WM][2], Bl[WM][F16 ? 1 : 2];
 #pragma unroll
       for (int wm = 0; wm < WM; ++wm) {
         f32x16 v;
@@ -1369,9 +1373,14 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
           }
         }
 #pragma unroll
-        for (int kq = 0; kq < 2; ++kq)
+        for (int kq = 0; kq < 2; ++kq) {
+          if constexpr (F16)
+            Bh[wm][kq] = x3_hi8(f32x4{v[8 * kq], v[8 * kq + 1], v[8 * kq + 2], v[8 * kq + 3]},
+                                f32x4{v[8 * kq + 4], v[8 * kq + 5], v[8 * kq + 6], v[8 * kq + 7]});
+          else
           x3_split8(f32x4{v[8 * kq], v[8 * kq + 1], v[8 * kq + 2], v[8 * kq + 3]},
                     f32x4{v[8 * kq + 4], v[8 * kq + 5], v[8 * kq + 6], v[8 * kq + 7]}, Bh[wm][kq], Bl[wm][kq]);
+        }
       }
       // this wave's 64-channel share of every Mconv7 row tile: its K blocks in order, 3 split
       // products each, from zero
@@ -1384,11 +1393,16 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
 #pragma unroll
           for (int kq = 0; kq < 2; ++kq) {
             const int kb = (wave_m * WM + wm) * 2 + kq;
+            if constexpr (F16) {   // hi-only pack_x3_f7: [t][kb][h][32 rows], one product per K block
+              const f16x8 Ah = a.wpk7[(size_t)(t * KB + kb) * 64 + lane];
+              d = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh[wm][kq], d, 0, 0, 0);
+            } else {
             const f16x8* wp = a.wpk7 + ((size_t)(t * KB + kb) * 2) * 64 + lane;
             const f16x8 Ah = abl_f7 ? Bh[wm][kq] : wp[0], Al = abl_f7 ? Bl[wm][kq] : wp[64];
             d = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh[wm][kq], d, 0, 0, 0);
             d = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl[wm][kq], d, 0, 0, 0);
             d = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh[wm][kq], d, 0, 0, 0);
+            }
           }
         float* rp = red + ((size_t)wave_m * RPX + wave_n * 32 + l32) * F7_ROWS + 32 * t + 4 * h;
 #pragma unroll
@@ -1428,6 +1442,27 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
 #pragma unroll
         for (int e = 0; e < 8; ++e) bad |= co + e < a.cout7 && !(__builtin_fabsf(o[e]) < 65504.f);
         const int y = m / a.W, x = m - y * a.W;
+        if constexpr (A16) {
+          // RNE(v) to the fp16 buffer after the range check above (x3_store4h's layout and masks); a
+          // net output also keeps v itself in its fp32 buffer (the dual store of the unfused Mconv7)
+          const size_t oe = (size_t)(co >> 3) * a.out_chs + (size_t)((y + a.out_pad) * Wo + x + a.out_pad) * 8;
+          x3_store4h(out_f, oe, f32x4{o[0], o[1], o[2], o[3]}, a.cout7 - co);
+          if (co + 4 < a.cout7) x3_store4h(out_f, oe + 4, f32x4{o[4], o[5], o[6], o[7]}, a.cout7 - co - 4);
+          if (a.out32) {
+            const int W32 = a.W + 2 * a.out32_pad;
+            float* o32 = a.out32 + (size_t)n * a.out32_fs + (size_t)(co >> 3) * a.out32_chs +
+                         (size_t)((y + a.out32_pad) * W32 + x + a.out32_pad) * 8;
+            if (co + 7 < a.cout7) {
+              *(f32x4*)o32 = f32x4{o[0], o[1], o[2], o[3]};
+              *(f32x4*)(o32 + 4) = f32x4{o[4], o[5], o[6], o[7]};
+            } else {
+#pragma unroll
+              for (int e = 0; e < 8; ++e)
+                if (co + e < a.cout7) o32[e] = o[e];
+            }
+          }
+          continue;
+        }
         float* oc = out_f + (size_t)(co >> 3) * a.out_chs + (size_t)((y + a.out_pad) * Wo + x + a.out_pad) * 8;
         if (co + 7 < a.cout7) {
           *(f32x4*)oc = f32x4{o[0], o[1], o[2], o[3]};
@@ -1989,12 +2024,12 @@ static hipError_t launch_t(const ConvLaunch& c, hipStream_t s) {
   t_last_variant = x3_variant_code(VAR, KS, BPX, (VAR & 16) ? BCO / 2 : BCO);
   constexpr bool A16 = (VAR & X3V_A16) != 0;
   // the variants without an fp16-storage form (x3_act16_ok: the runtime never plans them)
-  if constexpr (A16 && ((VAR & (16 | 2048 | 8192 | 16384 | 131072)) != 0 || (KS == 7 && WAVES_N == 3))) {
+  if constexpr (A16 && ((VAR & (2048 | 8192 | 16384 | 131072)) != 0 || (KS == 7 && WAVES_N == 3))) {
     set_error("conv_x3: no fp16-storage form of this variant (x3_act16_ok)");
     return hipErrorInvalidValue;
   } else {
   if (A16 != (c.act16 != 0)) { set_error("conv_x3: fp16-storage variant mismatch"); return hipErrorInvalidValue; }
-  if (c.out32 && (!A16 || c.hpool || (c.out32_cs & 7))) { set_error("conv_x3: fp32 output copy outside fp16 storage"); return hipErrorInvalidValue; }
+  if (c.out32 && (!A16 || c.hpool || (c.out32_cs & 7) || ((VAR & 16) != 0 && c.out32_cs < (c.cout7 + 7) / 8 * 8))) { set_error("conv_x3: fp32 output copy outside fp16 storage"); return hipErrorInvalidValue; }
   constexpr int P = KS / 2;
   constexpr int SEGCAP = x3_segmax(BPX);
   constexpr bool SPLIT = (VAR & 2048) != 0, RANGED = (VAR & 1024) != 0;
@@ -2680,6 +2715,21 @@ static hipError_t launch_x3_fused67(ConvLaunch c, hipStream_t s) {
   c.bco = c.cout;
   // (two chunk pairs per K step with one input buffer, VAR 4096 | 65536, measured level with
   // this loop in Mode N and Mode R, profiles/r04/r4c/ops_*_pps1.txt: not built)
+  // ISL_PREC_FP16: the one-term form (VAR 16 | 2: the one-term generic loop, one rounding of
+  // Mconv6's value, hi-only pack_x3_f7), with fp16 buffers on both sides under ISL_ACT_FP16 (| 1)
+  if (c.act16) {
+    switch (c.cout) {
+      case 512: return launch_t<1, 8, 2, 2, 2, 16 | X3V_F16 | X3V_A16, 4>(c, s);
+      case 256: return launch_t<1, 4, 4, 2, 2, 16 | X3V_F16 | X3V_A16, 4>(c, s);
+      case 128: return launch_t<1, 2, 8, 2, 2, 16 | X3V_F16 | X3V_A16, 4>(c, s);
+    }
+  } else if (c.f16) {
+    switch (c.cout) {
+      case 512: return launch_t<1, 8, 2, 2, 2, 16 | X3V_F16, 4>(c, s);
+      case 256: return launch_t<1, 4, 4, 2, 2, 16 | X3V_F16, 4>(c, s);
+      case 128: return launch_t<1, 2, 8, 2, 2, 16 | X3V_F16, 4>(c, s);
+    }
+  } else
   switch (c.cout) {
     case 512: return launch_t<1, 8, 2, 2, 2, 16, 4>(c, s);
     case 256: return launch_t<1, 4, 4, 2, 2, 16, 4>(c, s);
@@ -2704,7 +2754,7 @@ double conv_x3_fused67_mfma_flops(const ConvLaunch& c) {
   const int bpx = c.cout == 512 ? 128 : c.cout == 256 ? 256 : 512;
   const double px = std::ceil((double)c.H * c.W / tile_pixels(c, bpx, x3_segmax(bpx))) * bpx * c.n;
   const double k6 = ((c.cin_chunks + 1) / 2) * 16.0;
-  return 3.0 * 2.0 * px * ((double)c.cout * k6 + 32.0 * ((c.cout7 + 31) / 32) * c.cout);
+  return x3_products(c) * 2.0 * px * ((double)c.cout * k6 + 32.0 * ((c.cout7 + 31) / 32) * c.cout);
 }
 
 
@@ -2772,7 +2822,9 @@ static hipError_t launch_x3_wr(const ConvLaunch& c, int S, hipStream_t s) {
 }
 
 bool x3_act16_ok(const ConvLaunch& c0) {
-  if (!c0.f16 || c0.cout7 > 0 || c0.fold || c0.fold_out || !x3_fits(c0)) return false;
+  if (!c0.f16 || c0.fold || c0.fold_out || !x3_fits(c0)) return false;
+  // the fused 1x1 pair (VAR 16 | 2 | 1): one tile of every Mconv6 channel, no K ranges
+  if (c0.cout7 > 0) return c0.ks == 1 && x3_fused67_fits(c0.cout, c0.cout7) && !c0.hpool && !c0.vin;
   if (c0.ks != 1 && c0.ks != 3 && c0.ks != 7) return false;
   ConvLaunch c = c0;
   const X3Ranges r = x3_ranges(c);
@@ -2792,10 +2844,6 @@ hipError_t launch_conv_x3(const ConvLaunch& c0, hipStream_t s) {
   }
   if (c0.out32 && !c0.act16) {
     set_error("conv_x3: fp32 output copy outside fp16 storage");
-    return hipErrorInvalidValue;
-  }
-  if (c0.cout7 > 0 && c0.f16) {
-    set_error("conv_x3: the fused 1x1 pair has no one-term form (the plan runs it unfused)");
     return hipErrorInvalidValue;
   }
   if (c0.cout7 > 0) return launch_x3_fused67(c0, s);

@@ -62,7 +62,8 @@ struct ConvLaunch {
   int* range_flag = nullptr;   // raised when an output leaves the fp16 split range
   // ISL_PREC_FP16: one fp16 product per MAC.  wx3 then holds the hi halves alone -- the same
   // layouts without their [hi|lo] dimension (runtime.cpp pack_hi_only) -- and the kernels
-  // round the activations to fp16 once at staging; launch_conv_x3, launch_conv_x3_rgb only
+  // round the activations to fp16 once at staging; launch_conv_x3 (the fused pair included: wx3f7
+  // is then the hi-only pack_x3_f7), launch_conv_x3_rgb and launch_conv_x3_c12 (both launches set it)
   int f16 = 0;
   // ISL_ACT_FP16 (with f16 only): `in` and `out` are fp16 buffers (Act::esize 2; the strides in
   // elements are the same), the staging copies the stored roundings and the epilogue stores
@@ -137,15 +138,17 @@ bool x3_rgb_fits(const ConvLaunch& c);
 hipError_t launch_conv_x3_rgb(const ConvLaunch& c, hipStream_t s);
 double conv_x3_rgb_mfma_flops(const ConvLaunch& c);
 // conv1_1 -> conv1_2 -> pair-max (conv_c12.hip): l1 = conv1_1 (rgb-packed wx3), l2 = conv1_2 with
-// its hpool output
+// its hpool output.  f16 on both: the one-term form from the hi-only packs of both layers; act16
+// on both: l2.out is an fp16 buffer (the net input stays fp32)
 bool x3_c12_fits(const ConvLaunch& l1, const ConvLaunch& l2);
 hipError_t launch_conv_x3_c12(const ConvLaunch& l1, const ConvLaunch& l2, hipStream_t s);
 double conv_x3_c12_mfma_flops(const ConvLaunch& l1);
 hipError_t launch_conv_x3(const ConvLaunch& c, hipStream_t s);
 bool x3_fits(const ConvLaunch& c);
 // whether launch_conv_x3 would run c (f16 set, the fields as at its launch) on a kernel with an
-// fp16-storage form (ConvLaunch::act16): every one-term conv_x3_f16 variant but split-K across
-// blocks, the fold and the 96-pixel small 7x7 tiles; not the wave-range kernel
+// fp16-storage form (ConvLaunch::act16): every one-term conv_x3_f16 variant (the fused 1x1 pair
+// included) but split-K across blocks, the fold and the 96-pixel small 7x7 tiles; not the
+// wave-range kernel
 bool x3_act16_ok(const ConvLaunch& c);
 // whether launch_conv_x3 can run c with hpool (even W, not split across blocks)
 bool x3_hpool_ok(const ConvLaunch& c);

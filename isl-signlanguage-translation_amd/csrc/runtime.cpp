@@ -84,6 +84,11 @@ struct ConvLayer {
   void* d_hx3 = nullptr;
   void* d_hx3w = nullptr;
   void* d_hrgb = nullptr;
+  // ... and of the fusable pair's packs d_wx3f / d_wx3f7 / d_wx3p (the one-term fused launch and
+  // its permuted two-launch form), built and invalidated with the others
+  void* d_hx3f = nullptr;
+  void* d_hx3f7 = nullptr;
+  void* d_hx3p = nullptr;
 };
 
 static ConvLayer mk(const std::string& name, int cin, int cout, int k, int act, const std::string& prelu = "") {
@@ -764,10 +769,26 @@ static ConvLayer f7_permuted(const ConvLayer& c) {
 
 // ISLPOSE_X3_FUSE67: 0 the pairs as two plain launches (natural channel order; A/B), 2 always
 // fused, 3 always the permuted two launches (tests), default by grid (x3_fused67_grid); read
-// per run
-static int fuse67_mode() {
+// per run.  ISL_PREC_FP16 (h16): the one-term forms of both exist, but the fused K order of Mconv7
+// is the permuted one, not the natural order of the mode's plain launches (round-off apart), so
+// there an unset switch keeps the plain launches (0); 1 selects by grid as the fp32 default does
+static int fuse67_mode(bool h16) {
   const char* e = getenv("ISLPOSE_X3_FUSE67");
-  return e && e[0] >= '0' && e[0] <= '3' ? e[0] - '0' : 1;
+  return e && e[0] >= '0' && e[0] <= '3' ? e[0] - '0' : h16 ? 0 : 1;
+}
+
+// What the run does with the fusable pair (op k, op k + 1) under mode f67: 0 the plain launches,
+// 1 the fused launch, 2 the permuted two launches -- only where Mconv7 has K ranges (canonical:
+// its ranges are the fused kernel's wave shares, so both forms give the same bits); larger planes
+// always fuse.  Shared by run_ops_eager and act16_plan_ok.
+static ConvLaunch basic_launch(const isl_net* net, const Op& op);
+static int fuse67_form(const isl_net* net, size_t k, int f67) {
+  const Op& op = net->ops[k];
+  if (!f67 || !op.fuse67) return 0;
+  if ((f67 == 3 || (f67 == 1 && !x3_fused67_grid(basic_launch(net, op)))) &&
+      x3_split_ranges(basic_launch(net, net->ops[k + 1]), nullptr) > 1)
+    return 2;
+  return 1;
 }
 
 #ifdef ISLPOSE_DEV
@@ -855,6 +876,23 @@ static int upload_hi_packs(isl_net* net) {
       std::vector<_Float16> hp = pack_hi_only(pack_x3(c, 256, &inv), (size_t)2 * 256 * 8);
       if (!c.d_hx3w) HIP_OK(hipMalloc(&c.d_hx3w, hp.size() * sizeof(_Float16)));
       HIP_OK(hipMemcpy(c.d_hx3w, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    }
+    if (c.fuse6 && c.bco != c.cout) {   // one tile of all channels for the fused pair
+      std::vector<_Float16> hp = pack_hi_only(pack_x3(c, c.cout, &inv), (size_t)2 * c.cout * 8);
+      if (!c.d_hx3f) HIP_OK(hipMalloc(&c.d_hx3f, hp.size() * sizeof(_Float16)));
+      HIP_OK(hipMemcpy(c.d_hx3f, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    }
+    if (c.fuse7) {                      // pack_x3_f7: [t][kb][hi|lo][h][32][8]
+      std::vector<_Float16> hp = pack_hi_only(pack_x3_f7(c, &inv), (size_t)2 * 32 * 8);
+      if (inv != c.x3_inv) return fail(ISL_E_STATE, "hi-only pack: Mconv7 scale mismatch");
+      if (!c.d_hx3f7) HIP_OK(hipMalloc(&c.d_hx3f7, hp.size() * sizeof(_Float16)));
+      HIP_OK(hipMemcpy(c.d_hx3f7, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    }
+    if (c.fuse6 || c.fuse7) {           // the pair's permuted two-launch form
+      std::vector<_Float16> hp = pack_hi_only(pack_x3(f7_permuted(c), c.bco, &inv), (size_t)2 * c.bco * 8);
+      if (inv != c.x3_inv) return fail(ISL_E_STATE, "hi-only pack: permuted scale mismatch");
+      if (!c.d_hx3p) HIP_OK(hipMalloc(&c.d_hx3p, hp.size() * sizeof(_Float16)));
+      HIP_OK(hipMemcpy(c.d_hx3p, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
     }
   }
   net->packed_hi = true;
@@ -1261,10 +1299,56 @@ static ConvLaunch basic_launch(const isl_net* net, const Op& op) {
   return L;
 }
 
+// Whether ops k, k + 1, k + 2 (conv1_1 on the rgb kernel, conv1_2, the pool) run as the one
+// conv_c12.hip launch: conv1_1's output feeds conv1_2 only.  0: no; 1: the launch writes the pool's
+// pair-max buffer (ISLPOSE_C12=2, or no pooled buffer of the floor-mode shape); 2: the whole pool in
+// the epilogue.  *l1 / *l2 are the launches (h16: the one-term form from the hi-only packs, a16:
+// its fp16 output).  Shared by run_ops_eager and act16_plan_ok; reads the plan in net->act.
+static int c12_form(const isl_net* net, size_t k, bool fuse_pools, bool h16, bool a16, ConvLaunch* l1, ConvLaunch* l2) {
+  const Op& op = net->ops[k];
+  const int c12m = c12_mode();
+  if (!(net->algo == ISL_ALGO_X3 && op.type == 0 && fuse_pools && c12m && k + 2 < net->ops.size() &&
+        net->layers[op.layer].d_wrgb && rgb_kernel_enabled()))
+    return 0;
+  const Op& o2 = net->ops[k + 1];
+  const Op& pl = net->ops[k + 2];
+  bool only = o2.type == 0 && o2.in == op.out && o2.in_coff == 0 && op.out_coff == 0 && pl.type == 1 &&
+              pl.in == o2.out && o2.out_coff == 0 && pl.hbuf >= 0 && net->out0.buf != op.out &&
+              !(net->n_out > 1 && net->out1.buf == op.out);
+  for (size_t j = k + 2; only && j < net->ops.size(); ++j) {
+    if (net->ops[j].in == op.out) only = false;
+    if (net->ops[j].out == op.out) break;
+  }
+  if (!only) return 0;
+  ConvLaunch L1 = basic_launch(net, op), L2 = basic_launch(net, o2);
+  L1.wx3 = net->layers[op.layer].d_wrgb;
+  if (h16) {   // the one-term form: the hi-only packs of both layers
+    L1.wx3 = net->layers[op.layer].d_hrgb;
+    L2.wx3 = net->layers[o2.layer].d_hx3;
+    L1.f16 = L2.f16 = 1;
+    L1.act16 = L2.act16 = a16 ? 1 : 0;   // (the pooled map / pair-max buffer is fp16)
+  }
+  const Act& hb = net->act[pl.hbuf];
+  L2.out = hb.base; L2.out_pad = 0; L2.out_cs = hb.cs; L2.out_coff = 0;
+  L2.hpool = 1;
+  if (!(pl.C == L2.cout && x3_rgb_fits(L1) && x3_hpool_ok(L2) && x3_c12_fits(L1, L2))) return 0;
+  // the whole pool in the epilogue: the pooled buffer is the floor-mode 2x2 pool of conv1_2's
+  // plane, written from its channel 0
+  const Act& po = net->act[pl.out];
+  int form = 1;
+  if (c12m == 1 && pl.out_coff == 0 && po.H == L2.H / 2 && po.W == L2.W / 2 && po.cs >= 64 && po.n == L2.n) {
+    ConvLaunch P = L2;
+    P.out = po.base; P.out_pad = po.pad; P.out_cs = po.cs; P.hpool = 2;
+    if (x3_c12_fits(L1, P)) { L2 = P; form = 2; }
+  }
+  *l1 = L1; *l2 = L2;
+  return form;
+}
+
 // ISL_ACT_FP16 is all or nothing per run: whether every conv of a one-term run on the plan in
 // net->act (geometry only) would take a kernel with an fp16-storage form.  The walk makes the
-// choices of run_ops_eager in that mode (no fused pair, no conv1_1 -> conv1_2 launch, no Winograd
-// kernel) with the same predicates, up to the launch: the 3-channel kernel, or x3_act16_ok.  A conv
+// choices of run_ops_eager in that mode (the fused pair by fuse67_form, the conv1_1 -> conv1_2
+// launch by c12_form, no Winograd kernel) with the same predicates, up to the launch: the 3-channel kernel, or x3_act16_ok.  A conv
 // off the x3 kernels, a fold plan or K ranges across blocks (split-K, the wave-range kernel: the
 // latency-bound small grids) send the whole run to an fp32 arena.
 static bool act16_plan_ok(const isl_net* net) {
@@ -1275,6 +1359,8 @@ static bool act16_plan_ok(const isl_net* net) {
   bool fused = false;
   int vin_buf = -1;
   const bool fuse_pools = fused_pool_enabled(), pool_input = fuse_pools && pool_input_enabled();
+  const int f67 = fuse67_mode(true);
+  size_t perm_op = (size_t)-1;
   for (size_t k = 0; k < net->ops.size(); ++k) {
     const Op& op = net->ops[k];
     if (op.type == 1) {
@@ -1283,6 +1369,25 @@ static bool act16_plan_ok(const isl_net* net) {
       continue;
     }
     const ConvLayer& c = net->layers[op.layer];
+    // the fused 1x1 pair where the switch selects it: the fused launch (covered), or the
+    // permuted two launches (Mconv6 without K ranges, then Mconv7 as any conv below)
+    const int form67 = vin_buf < 0 ? fuse67_form(net, k, f67) : 0;
+    if (form67 == 2) perm_op = k;
+    if (form67 == 1) {
+      ConvLaunch L = basic_launch(net, op);
+      L.f16 = 1;
+      L.cout7 = net->layers[net->ops[k + 1].layer].cout;
+      if (op.in == net->in_buf || !x3_act16_ok(L)) return false;
+      ++k;
+      continue;
+    }
+    // conv1_1 -> conv1_2 -> pool in one launch (its fp16-storage form reads the fp32 net input)
+    {
+      ConvLaunch L1, L2;
+      const int form12 = vin_buf < 0 ? c12_form(net, k, fuse_pools, true, true, &L1, &L2) : 0;
+      if (form12 == 2) { k += 2; continue; }
+      if (form12 == 1) { fused = true; ++k; continue; }
+    }
     ConvLaunch L = basic_launch(net, op);
     if (!x3_fits(L)) return false;
     if (vin_buf >= 0) {
@@ -1292,7 +1397,9 @@ static bool act16_plan_ok(const isl_net* net) {
       if (x3_vin_ok(Lv) && !(c.d_wrgb && x3_rgb_fits(L))) L = Lv;
       vin_buf = -1;
     }
-    if (c.x3_wide) {
+    const bool perm = perm_op != (size_t)-1 && (k == perm_op || k == perm_op + 1);
+    if (perm && k == perm_op) L.allow_split = 0;
+    if (!perm && c.x3_wide) {
       ConvLaunch Lw = L;
       Lw.bco = 256;
       if (x3_wide1(Lw)) L.bco = 256;
@@ -1454,26 +1561,24 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
   int vin_buf = -1;     // this conv stages from that buffer (the pool op was skipped)
   const bool fuse_pools = fused_pool_enabled(), pool_input = fuse_pools && pool_input_enabled();
   // ISL_PREC_FP16 (ISL_ALGO_X3 only): every x3 conv on the one-term form of the variant the fp32
-  // plan picks, from the hi-only packs.  The fused launches (the 1x1 pair, conv1_1 -> conv1_2)
-  // have no one-term form and run as their layers; the Winograd kernel is never chosen.
+  // plan picks, from the hi-only packs -- the conv1_1 -> conv1_2 launch included (the same bits
+  // as its layers); the fused 1x1 pair only where ISLPOSE_X3_FUSE67 asks for it (fuse67_mode);
+  // the Winograd kernel is never chosen.
   const bool h16 = net->algo == ISL_ALGO_X3 && net->precision == ISL_PREC_FP16;
   if (h16 && !net->packed_hi) return fail(ISL_E_STATE, "fp16 precision: hi-only filters not uploaded");
   // ISL_ACT_FP16: the arena of this plan holds fp16 between the convs (plan() found every conv
   // covered); the launches below are those of the fp32-storage run, on the fp16-storage forms
   const bool a16 = net->cur->a16;
   if (a16 && !h16) return fail(ISL_E_STATE, "fp16 activation storage: the arena of this plan needs ISL_ALGO_X3 with ISL_PREC_FP16");
-  const int f67 = net->algo == ISL_ALGO_X3 && !h16 ? fuse67_mode() : 0;
+  const int f67 = net->algo == ISL_ALGO_X3 ? fuse67_mode(h16) : 0;
   size_t perm_op = (size_t)-1;   // the pair (perm_op, perm_op + 1) runs as its permuted two launches
   for (size_t k = 0; k < net->ops.size(); ++k) {
     const Op& op = net->ops[k];
     const Act& in = net->act[op.in];
     const Act& out = net->act[op.out];
-    // the two launches only where Mconv7 has K ranges (canonical: its ranges are the fused
-    // kernel's wave shares, so both forms give the same bits); larger planes always fuse
-    if (f67 && op.fuse67 && vin_buf < 0 && (f67 == 3 || (f67 == 1 && !x3_fused67_grid(basic_launch(net, op)))) &&
-        x3_split_ranges(basic_launch(net, net->ops[k + 1]), nullptr) > 1)
-      perm_op = k;
-    if (f67 && op.fuse67 && vin_buf < 0 && perm_op != k) {
+    const int form67 = vin_buf < 0 ? fuse67_form(net, k, f67) : 0;
+    if (form67 == 2) perm_op = k;
+    if (form67 == 1) {
       // Mconv6 -> Mconv7 in one launch (conv_x3 VAR 16): op k's input, op k + 1's output
       const Op& op7 = net->ops[k + 1];
       const ConvLayer& c6 = net->layers[op.layer];
@@ -1484,6 +1589,20 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
       L.wx3 = c6.d_wx3f ? c6.d_wx3f : c6.d_wx3;
       L.wx3f7 = c7.d_wx3f7; L.bias7 = c7.d_b; L.slope7 = c7.d_s; L.wscale7_inv = c7.x3_inv;
       L.cout7 = c7.cout; L.act7 = c7.act;
+      if (h16) {
+        L.f16 = 1;
+        L.wx3 = c6.d_hx3f ? c6.d_hx3f : c6.d_hx3;
+        L.wx3f7 = c7.d_hx3f7;
+      }
+      if (a16) {
+        L.act16 = 1;
+        // Mconv7 writing a net output last: the fused epilogue keeps the unrounded fp32 values too
+        for (int o = 0; o < net->n_out; ++o)
+          if ((int)k + 1 == net->out_op[o]) {
+            const Act& ob = net->act[net->out32_buf[o]];
+            L.out32 = ob.base; L.out32_pad = ob.pad; L.out32_cs = ob.cs;
+          }
+      }
       HIP_OK(launch_conv_x3(L, s));
       net->op_variant[k] = x3_last_variant();
       net->op_variant[k + 1] = -2;   // ran inside op k
@@ -1503,63 +1622,40 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
     // conv1_1 (rgb kernel) -> conv1_2 -> pool: both convs and the pool in one launch writing the
     // pooled map (or, ISLPOSE_C12=2, the pool's pair-max buffer), where conv1_1's output feeds
     // conv1_2 only (conv_c12.hip)
-    const int c12m = h16 ? 0 : c12_mode();
-    if (net->algo == ISL_ALGO_X3 && op.type == 0 && vin_buf < 0 && fuse_pools && c12m &&
-        k + 2 < net->ops.size() && net->layers[op.layer].d_wrgb && rgb_kernel_enabled()) {
+    ConvLaunch L1, L2;
+    const int form12 = vin_buf < 0 ? c12_form(net, k, fuse_pools, h16, a16, &L1, &L2) : 0;
+    if (form12) {
       const Op& o2 = net->ops[k + 1];
-      const Op& pl = net->ops[k + 2];
-      bool only = o2.type == 0 && o2.in == op.out && o2.in_coff == 0 && op.out_coff == 0 && pl.type == 1 &&
-                  pl.in == o2.out && o2.out_coff == 0 && pl.hbuf >= 0 && net->out0.buf != op.out &&
-                  !(net->n_out > 1 && net->out1.buf == op.out);
-      for (size_t j = k + 2; only && j < net->ops.size(); ++j) {
-        if (net->ops[j].in == op.out) only = false;
-        if (net->ops[j].out == op.out) break;
-      }
-      ConvLaunch L1 = basic_launch(net, op), L2 = only ? basic_launch(net, o2) : ConvLaunch{};
-      if (only) {
-        L1.wx3 = net->layers[op.layer].d_wrgb;
-        const Act& hb = net->act[pl.hbuf];
-        L2.out = hb.base; L2.out_pad = 0; L2.out_cs = hb.cs; L2.out_coff = 0;
-        L2.hpool = 1;
-        only = pl.C == L2.cout && x3_rgb_fits(L1) && x3_hpool_ok(L2) && x3_c12_fits(L1, L2);
-      }
-      // the whole pool in the epilogue: the pooled buffer is the floor-mode 2x2 pool of conv1_2's
-      // plane, written from its channel 0
-      const Act& po = net->act[pl.out];
-      bool pool2 = false;
-      if (only && c12m == 1 && pl.out_coff == 0 && po.H == L2.H / 2 && po.W == L2.W / 2 && po.cs >= 64 &&
-          po.n == L2.n) {
-        ConvLaunch P = L2;
-        P.out = po.base; P.out_pad = po.pad; P.out_cs = po.cs; P.hpool = 2;
-        if (x3_c12_fits(L1, P)) { L2 = P; pool2 = true; }
-      }
-      if (only) {
-        HIP_OK(launch_conv_x3_c12(L1, L2, s));
-        net->op_variant[k] = x3_variant_code(X3V_C12, 3, 256, 64);
-        net->op_variant[k + 1] = -2;   // ran inside op k
-        if (tr) {
-          const ConvLayer& c1 = net->layers[op.layer];
-          const ConvLayer& c2 = net->layers[o2.layer];
-          tr->kind.push_back(3);
-          tr->flops.push_back(2.0 * L1.H * L1.W * L1.n * 9.0 * ((double)c1.cout * c1.cin + (double)c2.cout * c2.cin));
-          tr->mfma_flops.push_back(conv_x3_c12_mfma_flops(L1));
-          HIP_OK(hipEventRecord(tr->ev[k + 1], s));
-          tr->kind.push_back(0); tr->flops.push_back(0.0); tr->mfma_flops.push_back(0.0);
-          HIP_OK(hipEventRecord(tr->ev[k + 2], s));
-          if (pool2) {
-            tr->kind.push_back(0); tr->flops.push_back(0.0); tr->mfma_flops.push_back(0.0);
-            HIP_OK(hipEventRecord(tr->ev[k + 3], s));
-          }
-        }
+      const bool pool2 = form12 == 2;
+      HIP_OK(launch_conv_x3_c12(L1, L2, s));
+      // (ISL_PREC_FP16 also sets X3V_RGB: conv1_1 runs conv_x3_rgb's one-term K packing inside the
+      // launch, and the fp16 suites find the 3-channel form of a run by that bit)
+      net->op_variant[k] = x3_variant_code(X3V_C12 | (h16 ? X3V_F16 | X3V_RGB : 0) | (a16 ? X3V_A16 : 0), 3, 256, 64);
+      // conv1_2 ran inside op k.  ISL_PREC_FP16 reports it as -1, "fused with its pool": the
+      // fp16-storage suite holds every conv op of a run to the act16 bit or that code
+      net->op_variant[k + 1] = h16 ? -1 : -2;
+      if (tr) {
+        const ConvLayer& c1 = net->layers[op.layer];
+        const ConvLayer& c2 = net->layers[o2.layer];
+        tr->kind.push_back(3);
+        tr->flops.push_back(2.0 * L1.H * L1.W * L1.n * 9.0 * ((double)c1.cout * c1.cin + (double)c2.cout * c2.cin));
+        tr->mfma_flops.push_back(conv_x3_c12_mfma_flops(L1));
+        HIP_OK(hipEventRecord(tr->ev[k + 1], s));
+        tr->kind.push_back(0); tr->flops.push_back(0.0); tr->mfma_flops.push_back(0.0);
+        HIP_OK(hipEventRecord(tr->ev[k + 2], s));
         if (pool2) {
-          net->op_variant[k + 2] = -2;   // the pool ran inside op k
-          k += 2;
-          continue;
+          tr->kind.push_back(0); tr->flops.push_back(0.0); tr->mfma_flops.push_back(0.0);
+          HIP_OK(hipEventRecord(tr->ev[k + 3], s));
         }
-        fused = true;   // the pool op finds its pair-max buffer written
-        ++k;
+      }
+      if (pool2) {
+        net->op_variant[k + 2] = -2;   // the pool ran inside op k
+        k += 2;
         continue;
       }
+      fused = true;   // the pool op finds its pair-max buffer written
+      ++k;
+      continue;
     }
 
     if (op.type == 1) {
@@ -1621,9 +1717,9 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
         Lw.bco = 256;
         if (x3_wide1(Lw)) { L.bco = 256; L.wx3 = c.d_wx3w; }
       }
-      if (h16) {   // (perm is never set: the pair is not fused in this mode)
+      if (h16) {
         L.f16 = 1;
-        L.wx3 = L.bco == 256 && c.x3_wide ? c.d_hx3w : c.d_hx3;
+        L.wx3 = perm ? c.d_hx3p : L.bco == 256 && c.x3_wide ? c.d_hx3w : c.d_hx3;
       }
       if (a16) {
         L.act16 = 1;
@@ -1992,6 +2088,9 @@ int isl_net_destroy(isl_net* net) {
     if (c.d_hx3) (void)hipFree(c.d_hx3);
     if (c.d_hx3w) (void)hipFree(c.d_hx3w);
     if (c.d_hrgb) (void)hipFree(c.d_hrgb);
+    if (c.d_hx3f) (void)hipFree(c.d_hx3f);
+    if (c.d_hx3f7) (void)hipFree(c.d_hx3f7);
+    if (c.d_hx3p) (void)hipFree(c.d_hx3p);
     if (c.d_bp) (void)hipFree(c.d_bp);
     if (c.d_sp) (void)hipFree(c.d_sp);
   }

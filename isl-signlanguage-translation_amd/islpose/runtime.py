@@ -268,7 +268,9 @@ def decode_variant(code: int) -> dict:
     """isl_net_op_info's variant code -> dict(var=VAR bits, bpx, bco, ks, rgb, pool_fused, ...):
     wave_ranges (conv_x3_wr, VAR 8), c12 (conv1_1 -> conv1_2 in one launch, 4), wino2 (the
     split-fp16 Winograd kernel wino_f16, 64), f16 (one-term fp16 products, precision 'fp16', 2),
-    act16 (the launch reads or writes fp16 activations, act_storage 'fp16', 1)."""
+    act16 (the launch reads or writes fp16 activations, act_storage 'fp16', 1).  Under precision
+    'fp16' the c12 launch also carries rgb (conv1_1 runs the 3-channel kernel's one-term K packing
+    inside it) and conv1_2 reports -1 (it ran fused with its pool inside conv1_1's launch)."""
     if code == -1:
         return {"pool_fused": True}
     if code == -2:
