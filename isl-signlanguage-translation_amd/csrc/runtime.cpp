@@ -780,13 +780,13 @@ static int fuse67_mode(bool h16) {
 // What the run does with the fusable pair (op k, op k + 1) under mode f67: 0 the plain launches,
 // 1 the fused launch, 2 the permuted two launches -- only where Mconv7 has K ranges (canonical:
 // its ranges are the fused kernel's wave shares, so both forms give the same bits); larger planes
-// always fuse.  Shared by run_ops_eager and act16_plan_ok.
-static ConvLaunch basic_launch(const isl_net* net, const Op& op);
-static int fuse67_form(const isl_net* net, size_t k, int f67) {
+// always fuse.  `act`: the plan's geometry.
+static ConvLaunch basic_launch(const isl_net* net, const std::vector<Act>& act, const Op& op);
+static int fuse67_form(const isl_net* net, const std::vector<Act>& act, size_t k, int f67) {
   const Op& op = net->ops[k];
   if (!f67 || !op.fuse67) return 0;
-  if ((f67 == 3 || (f67 == 1 && !x3_fused67_grid(basic_launch(net, op)))) &&
-      x3_split_ranges(basic_launch(net, net->ops[k + 1]), nullptr) > 1)
+  if ((f67 == 3 || (f67 == 1 && !x3_fused67_grid(basic_launch(net, act, op)))) &&
+      x3_split_ranges(basic_launch(net, act, net->ops[k + 1]), nullptr) > 1)
     return 2;
   return 1;
 }
@@ -1108,19 +1108,14 @@ static std::vector<Act> layout_acts(const isl_net* net, int n, int h, int w, boo
   return act;
 }
 
-static bool act16_plan_ok(const isl_net* net);
+static bool act16_plan_ok(const isl_net* net, const std::vector<Act>& geo);
 
 // Whether an n-frame run at h x w stores its activations as fp16: the switch is on, it applies
-// (ISL_ALGO_X3 with ISL_PREC_FP16) and every conv of the run would take a kernel with an
-// fp16-storage form -- all or nothing, decided before the first launch with the predicates the
-// launches use (act16_plan_ok).
-static bool act16_for(isl_net* net, int n, int h, int w) {
+// (ISL_ALGO_X3 with ISL_PREC_FP16) and every step of the run's launch plan on the fp16 geometry
+// has an fp16-storage form -- all or nothing, decided before the first launch (act16_plan_ok).
+static bool act16_for(const isl_net* net, int n, int h, int w) {
   if (net->act_storage != ISL_ACT_FP16 || net->algo != ISL_ALGO_X3 || net->precision != ISL_PREC_FP16) return false;
-  std::vector<Act> geo = layout_acts(net, n, h, w, true);
-  net->act.swap(geo);            // the predicates read the plan's geometry from net->act
-  const bool ok = act16_plan_ok(net);
-  net->act.swap(geo);
-  return ok;
+  return act16_plan_ok(net, layout_acts(net, n, h, w, true));
 }
 
 static int plan(isl_net* net, int n, int h, int w, hipStream_t s) {
@@ -1253,19 +1248,19 @@ static bool pool_input_enabled() {
 // Pool op k may leave its output unwritten and hand its pair-max buffer to op k+1 (vin):
 // op k+1 is an x3 conv (not the 3-channel rgb kernel) reading the whole pooled buffer,
 // which nothing else reads and which is no net output.
-static bool pool_into_next_conv(const isl_net* net, size_t k) {
+static bool pool_into_next_conv(const isl_net* net, const std::vector<Act>& act, size_t k) {
   const Op& op = net->ops[k];
   if (k + 1 >= net->ops.size() || net->algo != ISL_ALGO_X3) return false;
   const Op& nx = net->ops[k + 1];
   if (nx.type != 0 || nx.in != op.out || nx.in_coff != 0) return false;
   const ConvLayer& c = net->layers[nx.layer];
-  if (c.cin_phys / 8 == 1 || net->act[op.out].pad < c.k / 2 || net->act[op.out].cs != (op.C + 7) / 8 * 8)
+  if (c.cin_phys / 8 == 1 || act[op.out].pad < c.k / 2 || act[op.out].cs != (op.C + 7) / 8 * 8)
     return false;
   if (net->out0.buf == op.out || (net->n_out > 1 && net->out1.buf == op.out)) return false;
   // the staging addresses the pair-max buffer as [chunk][2H][W][8] of the pooled H x W: a
   // pre-pool plane of odd height (floor-mode pool drops its last row) has another chunk
   // stride, so it takes vpool2 (e.g. 8 x 372 x 656, level-2 height 93)
-  if (net->act[op.in].H != 2 * net->act[op.out].H || net->act[op.in].W != 2 * net->act[op.out].W) return false;
+  if (act[op.in].H != 2 * act[op.out].H || act[op.in].W != 2 * act[op.out].W) return false;
   for (size_t j = 0; j < net->ops.size(); ++j)
     if (j != k + 1 && (net->ops[j].in == op.out || (j != k && net->ops[j].out == op.out))) return false;
   return true;
@@ -1283,10 +1278,11 @@ static bool fold_enabled() {
 #endif
 }
 
-// The conv launch of op k before the per-run adjustments (pools, wide 1x1 tiles, fold)
-static ConvLaunch basic_launch(const isl_net* net, const Op& op) {
-  const Act& in = net->act[op.in];
-  const Act& out = net->act[op.out];
+// The conv launch of an op on the geometry `act` before the per-run adjustments (pools, wide 1x1
+// tiles, fold)
+static ConvLaunch basic_launch(const isl_net* net, const std::vector<Act>& act, const Op& op) {
+  const Act& in = act[op.in];
+  const Act& out = act[op.out];
   const ConvLayer& c = net->layers[op.layer];
   ConvLaunch L;
   L.in = in.base; L.in_pad = in.pad; L.in_cs = in.cs; L.in_coff = op.in_coff;
@@ -1303,8 +1299,9 @@ static ConvLaunch basic_launch(const isl_net* net, const Op& op) {
 // conv_c12.hip launch: conv1_1's output feeds conv1_2 only.  0: no; 1: the launch writes the pool's
 // pair-max buffer (ISLPOSE_C12=2, or no pooled buffer of the floor-mode shape); 2: the whole pool in
 // the epilogue.  *l1 / *l2 are the launches (h16: the one-term form from the hi-only packs, a16:
-// its fp16 output).  Shared by run_ops_eager and act16_plan_ok; reads the plan in net->act.
-static int c12_form(const isl_net* net, size_t k, bool fuse_pools, bool h16, bool a16, ConvLaunch* l1, ConvLaunch* l2) {
+// its fp16 output) on the geometry `act`.
+static int c12_form(const isl_net* net, const std::vector<Act>& act, size_t k, bool fuse_pools, bool h16, bool a16,
+                    ConvLaunch* l1, ConvLaunch* l2) {
   const Op& op = net->ops[k];
   const int c12m = c12_mode();
   if (!(net->algo == ISL_ALGO_X3 && op.type == 0 && fuse_pools && c12m && k + 2 < net->ops.size() &&
@@ -1320,7 +1317,7 @@ static int c12_form(const isl_net* net, size_t k, bool fuse_pools, bool h16, boo
     if (net->ops[j].out == op.out) break;
   }
   if (!only) return 0;
-  ConvLaunch L1 = basic_launch(net, op), L2 = basic_launch(net, o2);
+  ConvLaunch L1 = basic_launch(net, act, op), L2 = basic_launch(net, act, o2);
   L1.wx3 = net->layers[op.layer].d_wrgb;
   if (h16) {   // the one-term form: the hi-only packs of both layers
     L1.wx3 = net->layers[op.layer].d_hrgb;
@@ -1328,13 +1325,13 @@ static int c12_form(const isl_net* net, size_t k, bool fuse_pools, bool h16, boo
     L1.f16 = L2.f16 = 1;
     L1.act16 = L2.act16 = a16 ? 1 : 0;   // (the pooled map / pair-max buffer is fp16)
   }
-  const Act& hb = net->act[pl.hbuf];
+  const Act& hb = act[pl.hbuf];
   L2.out = hb.base; L2.out_pad = 0; L2.out_cs = hb.cs; L2.out_coff = 0;
   L2.hpool = 1;
   if (!(pl.C == L2.cout && x3_rgb_fits(L1) && x3_hpool_ok(L2) && x3_c12_fits(L1, L2))) return 0;
   // the whole pool in the epilogue: the pooled buffer is the floor-mode 2x2 pool of conv1_2's
   // plane, written from its channel 0
-  const Act& po = net->act[pl.out];
+  const Act& po = act[pl.out];
   int form = 1;
   if (c12m == 1 && pl.out_coff == 0 && po.H == L2.H / 2 && po.W == L2.W / 2 && po.cs >= 64 && po.n == L2.n) {
     ConvLaunch P = L2;
@@ -1345,79 +1342,207 @@ static int c12_form(const isl_net* net, size_t k, bool fuse_pools, bool h16, boo
   return form;
 }
 
-// ISL_ACT_FP16 is all or nothing per run: whether every conv of a one-term run on the plan in
-// net->act (geometry only) would take a kernel with an fp16-storage form.  The walk makes the
-// choices of run_ops_eager in that mode (the fused pair by fuse67_form, the conv1_1 -> conv1_2
-// launch by c12_form, no Winograd kernel) with the same predicates, up to the launch: the 3-channel kernel, or x3_act16_ok.  A conv
-// off the x3 kernels, a fold plan or K ranges across blocks (split-K, the wave-range kernel: the
-// latency-bound small grids) send the whole run to an fp32 arena.
-static bool act16_plan_ok(const isl_net* net) {
+// One step of a run's launch plan (plan_steps): a pool, a conv launch, or a launch that swallows
+// the ops after it (the fused 1x1 pair: 2 ops; conv1_1 -> conv1_2 [-> pool]: 2 or 3).
+struct Step {
+  enum Kind {
+    POOL, VPOOL,     // maxpool2 / the row-pair half of a pool whose conv wrote the pair-max buffer
+    POOL_DEFERRED,   // no launch: the next conv stages from the pair-max buffer (ConvLaunch::vin)
+    X3, X3_RGB, W2, PAIR, C12,
+    DIRECT, WINO,    // from here on: convs off the x3 kernels -- the fp32 kernels
+#ifdef ISLPOSE_DEV
+    WINO_X3,
+#endif
+  };
+  Kind kind = POOL;
+  int op = 0, nops = 1;      // the first op and how many the step covers
+  ConvLaunch L{}, L2{};      // the launch (C12: conv1_1 and conv1_2), but for the split-K workspace and fold pointers
+  int code[3] = {0, 0, 0};   // op_variant of the covered ops (the first: X3, X3_RGB, PAIR report x3_last_variant())
+  int late_pool = -1;        // a deferred pool this conv has no pooled-input variant for: its vpool2 runs first
+  bool covered = false;      // the step has an fp16-storage form (ISL_ACT_FP16)
+  const char* error = nullptr;   // ISL_E_STATE: the run cannot take this step
+};
+
+// The launch plan of a run on the geometry `act`: what every op becomes, in order, with its
+// launch filled in.  A pure host function of its arguments and the ISLPOSE_* switches -- the run
+// (run_ops_eager, on net->act) and the storage decision (act16_plan_ok, on a trial geometry
+// without addresses) both read it.  h16: ISL_PREC_FP16 (ISL_ALGO_X3 only), every x3 conv on the
+// one-term form of the variant the fp32 plan picks, from the hi-only packs -- the conv1_1 ->
+// conv1_2 launch included (the same bits as its layers); the fused 1x1 pair only where
+// ISLPOSE_X3_FUSE67 asks for it (fuse67_mode); the Winograd kernel is never chosen.  a16: `act`
+// holds fp16 between the convs, the launches are those of the fp32-storage run on the
+// fp16-storage forms.  far: the arena whose fold plan (plan_fold) applies, or null.
+static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& act, bool h16, bool a16,
+                                    const isl_net::Arena* far) {
+  const size_t nops = net->ops.size();
+  std::vector<Step> steps;
+  steps.reserve(nops);
+  bool fused = false;   // the previous conv wrote the pair-max buffer of this pool
+  int vin_buf = -1;     // this conv stages from that buffer (the pool op was skipped)
+  const bool fuse_pools = fused_pool_enabled(), pool_input = fuse_pools && pool_input_enabled();
+  const int f67 = net->algo == ISL_ALGO_X3 ? fuse67_mode(h16) : 0;
+  size_t perm_op = (size_t)-1;   // the pair (perm_op, perm_op + 1) runs as its permuted two launches
+  // fp16 storage: the layer that writes a net output last also keeps the unrounded fp32 values
+  auto store16 = [&](ConvLaunch& L, size_t writer) {
+    L.act16 = 1;
+    for (int o = 0; o < net->n_out; ++o)
+      if ((int)writer == net->out_op[o]) {
+        const Act& ob = act[net->out32_buf[o]];
+        L.out32 = ob.base; L.out32_pad = ob.pad; L.out32_cs = ob.cs;
+      }
+  };
+  for (size_t k = 0; k < nops; k += steps.back().nops) {
+    const Op& op = net->ops[k];
+    steps.emplace_back();
+    Step& st = steps.back();
+    ConvLaunch& L = st.L;
+    st.op = (int)k;
+    const int form67 = vin_buf < 0 ? fuse67_form(net, act, k, f67) : 0;
+    if (form67 == 2) perm_op = k;
+    if (form67 == 1) {
+      // Mconv6 -> Mconv7 in one launch (conv_x3 VAR 16): op k's input, op k + 1's output
+      const Op& op7 = net->ops[k + 1];
+      const ConvLayer& c6 = net->layers[op.layer];
+      const ConvLayer& c7 = net->layers[op7.layer];
+      const Act& o7 = act[op7.out];
+      L = basic_launch(net, act, op);
+      L.out = o7.base; L.out_pad = o7.pad; L.out_cs = o7.cs; L.out_coff = op7.out_coff;
+      L.wx3 = c6.d_wx3f ? c6.d_wx3f : c6.d_wx3;
+      L.wx3f7 = c7.d_wx3f7; L.bias7 = c7.d_b; L.slope7 = c7.d_s; L.wscale7_inv = c7.x3_inv;
+      L.cout7 = c7.cout; L.act7 = c7.act;
+      if (h16) {
+        L.f16 = 1;
+        L.wx3 = c6.d_hx3f ? c6.d_hx3f : c6.d_hx3;
+        L.wx3f7 = c7.d_hx3f7;
+      }
+      if (a16) store16(L, k + 1);
+      st.kind = Step::PAIR;
+      st.nops = 2;
+      st.code[1] = -2;   // ran inside op k
+      // (the net input is fp32 in every arena: only the 3-channel kernel reads it)
+      st.covered = op.in != net->in_buf && x3_act16_ok(L);
+      continue;
+    }
+
+    // conv1_1 (rgb kernel) -> conv1_2 -> pool: both convs and the pool in one launch writing the
+    // pooled map (or, ISLPOSE_C12=2, the pool's pair-max buffer), where conv1_1's output feeds
+    // conv1_2 only (conv_c12.hip; its fp16-storage form reads the fp32 net input)
+    const int form12 = vin_buf < 0 ? c12_form(net, act, k, fuse_pools, h16, a16, &st.L, &st.L2) : 0;
+    if (form12) {
+      st.kind = Step::C12;
+      st.nops = form12 == 2 ? 3 : 2;   // 2: the pool ran inside op k too; 1: the pool op finds its pair-max buffer written
+      if (form12 == 1) fused = true;
+      // (ISL_PREC_FP16 also sets X3V_RGB: conv1_1 runs conv_x3_rgb's one-term K packing inside the
+      // launch, and the fp16 suites find the 3-channel form of a run by that bit)
+      st.code[0] = x3_variant_code(X3V_C12 | (h16 ? X3V_F16 | X3V_RGB : 0) | (a16 ? X3V_A16 : 0), 3, 256, 64);
+      // conv1_2 ran inside op k.  ISL_PREC_FP16 reports it as -1, "fused with its pool": the
+      // fp16-storage suite holds every conv op of a run to the act16 bit or that code
+      st.code[1] = h16 ? -1 : -2;
+      st.code[2] = -2;
+      st.covered = true;
+      continue;
+    }
+
+    if (op.type == 1) {
+      // deferred: the next conv either stages from the pair-max buffer or runs vpool2 first
+      if (fused && pool_input && pool_into_next_conv(net, act, k)) {
+        vin_buf = (int)k;
+        st.kind = Step::POOL_DEFERRED;
+        st.code[0] = -1;
+      } else {
+        st.kind = fused ? Step::VPOOL : Step::POOL;
+      }
+      fused = false;
+      st.covered = true;
+      continue;
+    }
+    const ConvLayer& c = net->layers[op.layer];
+    L = basic_launch(net, act, op);
+    if (net->algo == ISL_ALGO_WINO && c.wbco) {
+      L.wpk = c.d_wu; L.bco = c.wbco;
+      st.kind = Step::WINO;
+#ifdef ISLPOSE_DEV
+    } else if (net->algo == ISL_ALGO_X3 && c.d_wux3 && x3_wino_enabled() && vin_buf < 0) {
+      L.wx3 = c.d_wux3; L.wscale_inv = c.wx3_inv;
+      st.kind = Step::WINO_X3;
+#endif
+    } else if (net->algo == ISL_ALGO_X3 && x3_fits(L)) {
+      if (vin_buf >= 0) {   // the preceding pool's row-pair max happens in this conv's staging
+        const Act& hb = act[net->ops[vin_buf].hbuf];
+        ConvLaunch Lv = L;
+        Lv.in = hb.base; Lv.in_cs = hb.cs; Lv.in_coff = 0; Lv.vin = 1;
+        if (x3_vin_ok(Lv) && !(c.d_wrgb && x3_rgb_fits(L))) L = Lv;
+        else st.late_pool = vin_buf;   // no variant: the pool after all
+        vin_buf = -1;
+      }
+      const bool perm = k == perm_op || (perm_op != (size_t)-1 && k == perm_op + 1);
+      if (perm && k == perm_op) {
+        // Mconv6 of the pair's two launches: output channels in the fused K order, its K
+        // summed in one sequence as the fused kernel does (no ranges)
+        L.wx3 = c.d_wx3p; L.bias = c.d_bp; L.slope = c.d_sp;
+        L.allow_split = 0;
+      } else if (perm) {
+        L.wx3 = c.d_wx3p;   // Mconv7 reading them through that channel map
+      } else if (c.x3_wide) {   // 256-channel tiles, two pairs per step, where the grid is big enough
+        ConvLaunch Lw = L;
+        Lw.bco = 256;
+        if (x3_wide1(Lw)) { L.bco = 256; L.wx3 = c.d_wx3w; }
+      }
+      if (h16) {
+        L.f16 = 1;
+        L.wx3 = perm ? c.d_hx3p : L.bco == 256 && c.x3_wide ? c.d_hx3w : c.d_hx3;
+      }
+      if (a16) store16(L, k);
+      // the next op pools this conv's output: write pair maxima to its half-width buffer
+      if (k + 1 < nops && net->ops[k + 1].type == 1 && net->ops[k + 1].in == op.out && op.out_coff == 0 &&
+          net->ops[k + 1].C == c.cout && fuse_pools && x3_hpool_ok(L)) {
+        const Act& hb = act[net->ops[k + 1].hbuf];
+        L.out = hb.base; L.out_pad = 0; L.out_cs = hb.cs; L.out_coff = 0;
+        L.hpool = 1;
+        fused = true;
+      }
+      // the Winograd kernel: plain 3x3 launches -- no pool on either side (decided from the graph,
+      // not from whether the pool is fused, so the pool switches never change a conv's arithmetic),
+      // no fold, no K ranges
+      const bool pool_side = (k > 0 && net->ops[k - 1].type == 1 && net->ops[k - 1].out == op.in) ||
+                             (k + 1 < nops && net->ops[k + 1].type == 1 && net->ops[k + 1].in == op.out);
+      const bool folds = far && (far->fold_ws_off[k] >= 0 || far->fold_tab_off[k] >= 0);
+      ConvLaunch Lw = L;
+      Lw.wx3 = c.d_ww;
+      Lw.wscale_inv = c.ww_inv;
+      if (!h16 && !perm && !pool_side && w2_enabled(L) && c.d_ww && !L.vin && !L.hpool && !folds &&
+          x3_split_ranges(L, nullptr) <= 1 && wino_f16_fits(Lw)) {
+        L = Lw;
+        st.kind = Step::W2;
+        st.code[0] = x3_variant_code(X3V_W2, 3, 128, 64);
+      } else if (c.d_wrgb && x3_rgb_fits(L) && rgb_kernel_enabled() && !L.vin) {
+        L.wx3 = h16 ? c.d_hrgb : c.d_wrgb;
+        st.kind = Step::X3_RGB;
+        st.covered = true;
+      } else {
+        // (the net input is fp32 in every arena: only the 3-channel kernel reads it)
+        st.kind = Step::X3;
+        st.covered = !folds && op.in != net->in_buf && x3_act16_ok(L);
+      }
+    } else {
+      st.kind = Step::DIRECT;
+    }
+    if (vin_buf >= 0) st.error = "pooled-input staging: the conv after a skipped pool did not take it";
+  }
+  return steps;
+}
+
+// ISL_ACT_FP16 is all or nothing per run: whether every step of a one-term run on the geometry
+// `geo` (no addresses) has an fp16-storage form.  A conv off the x3 kernels, a fold plan or K
+// ranges across blocks (split-K, the wave-range kernel: the latency-bound small grids) send the
+// whole run to an fp32 arena.
+static bool act16_plan_ok(const isl_net* net, const std::vector<Act>& geo) {
   if (fold_enabled()) return false;
 #ifdef ISLPOSE_DEV
   if (x3_wino_enabled()) return false;
 #endif
-  bool fused = false;
-  int vin_buf = -1;
-  const bool fuse_pools = fused_pool_enabled(), pool_input = fuse_pools && pool_input_enabled();
-  const int f67 = fuse67_mode(true);
-  size_t perm_op = (size_t)-1;
-  for (size_t k = 0; k < net->ops.size(); ++k) {
-    const Op& op = net->ops[k];
-    if (op.type == 1) {
-      if (fused && pool_input && pool_into_next_conv(net, k)) vin_buf = (int)k;
-      fused = false;
-      continue;
-    }
-    const ConvLayer& c = net->layers[op.layer];
-    // the fused 1x1 pair where the switch selects it: the fused launch (covered), or the
-    // permuted two launches (Mconv6 without K ranges, then Mconv7 as any conv below)
-    const int form67 = vin_buf < 0 ? fuse67_form(net, k, f67) : 0;
-    if (form67 == 2) perm_op = k;
-    if (form67 == 1) {
-      ConvLaunch L = basic_launch(net, op);
-      L.f16 = 1;
-      L.cout7 = net->layers[net->ops[k + 1].layer].cout;
-      if (op.in == net->in_buf || !x3_act16_ok(L)) return false;
-      ++k;
-      continue;
-    }
-    // conv1_1 -> conv1_2 -> pool in one launch (its fp16-storage form reads the fp32 net input)
-    {
-      ConvLaunch L1, L2;
-      const int form12 = vin_buf < 0 ? c12_form(net, k, fuse_pools, true, true, &L1, &L2) : 0;
-      if (form12 == 2) { k += 2; continue; }
-      if (form12 == 1) { fused = true; ++k; continue; }
-    }
-    ConvLaunch L = basic_launch(net, op);
-    if (!x3_fits(L)) return false;
-    if (vin_buf >= 0) {
-      const Act& hb = net->act[net->ops[vin_buf].hbuf];
-      ConvLaunch Lv = L;
-      Lv.in_cs = hb.cs; Lv.in_coff = 0; Lv.vin = 1;
-      if (x3_vin_ok(Lv) && !(c.d_wrgb && x3_rgb_fits(L))) L = Lv;
-      vin_buf = -1;
-    }
-    const bool perm = perm_op != (size_t)-1 && (k == perm_op || k == perm_op + 1);
-    if (perm && k == perm_op) L.allow_split = 0;
-    if (!perm && c.x3_wide) {
-      ConvLaunch Lw = L;
-      Lw.bco = 256;
-      if (x3_wide1(Lw)) L.bco = 256;
-    }
-    L.f16 = 1;
-    if (k + 1 < net->ops.size() && net->ops[k + 1].type == 1 && net->ops[k + 1].in == op.out && op.out_coff == 0 &&
-        net->ops[k + 1].C == c.cout && fuse_pools && x3_hpool_ok(L)) {
-      L.out_pad = 0; L.out_cs = net->act[net->ops[k + 1].hbuf].cs; L.out_coff = 0;
-      L.hpool = 1;
-      fused = true;
-    }
-    if (c.d_wrgb && x3_rgb_fits(L) && rgb_kernel_enabled() && !L.vin) {
-      if (op.out == net->in_buf) return false;
-      continue;
-    }
-    // (the net input is fp32 in every arena: only the 3-channel kernel reads it)
-    if (op.in == net->in_buf || !x3_act16_ok(L)) return false;
-  }
+  for (const Step& st : plan_steps(net, geo, true, true, nullptr))
+    if (!st.covered) return false;
   return true;
 }
 
@@ -1438,7 +1563,7 @@ static int plan_fold(isl_net* net, hipStream_t s) {
   ar.fold_n = net->pn;
   ar.fold_mode = mode;
   if (!mode) return ISL_OK;
-  auto is_conv_x3 = [&](size_t k) { return net->ops[k].type == 0 && x3_fits(basic_launch(net, net->ops[k])); };
+  auto is_conv_x3 = [&](size_t k) { return net->ops[k].type == 0 && x3_fits(basic_launch(net, net->act, net->ops[k])); };
   // a consumer may fold only on the generic loop with no pool on either side
   auto consumer_ok = [&](size_t j) {
     if (!is_conv_x3(j)) return false;
@@ -1447,7 +1572,7 @@ static int plan_fold(isl_net* net, hipStream_t s) {
     if (j + 1 < nops && net->ops[j + 1].type == 1 && net->ops[j + 1].in == op.out) return false;
     const ConvLayer& c = net->layers[op.layer];
     if (c.d_wrgb) return false;
-    return x3_fold_ok(basic_launch(net, op));
+    return x3_fold_ok(basic_launch(net, net->act, op));
   };
   struct Prod { size_t k; int S; long long off; std::vector<size_t> cons; };
   std::vector<Prod> prods;
@@ -1457,7 +1582,7 @@ static int plan_fold(isl_net* net, hipStream_t s) {
     if (!is_conv_x3(k)) continue;
     const ConvLayer& c = net->layers[op.layer];
     if (c.cout % 8 || c.d_wrgb) continue;
-    ConvLaunch L = basic_launch(net, op);
+    ConvLaunch L = basic_launch(net, net->act, op);
     bool across = false;
     const int S = x3_split_ranges(L, &across);
     if (S < 2 || !across) continue;
@@ -1542,6 +1667,42 @@ static int plan_fold(isl_net* net, hipStream_t s) {
   return ISL_OK;
 }
 
+// The timing record of a step that has run: kind (isl_net_timing's op kinds: 0 no conv, 1 fp32
+// direct, 2 fp32 Winograd, 3 split-fp16 direct, 4 wino_x3, 5 wino_f16), FLOPs and MFMA FLOPs on
+// its first op, and one event per covered op -- the ops a launch swallowed are empty intervals.
+static int record_step(const isl_net* net, isl_net::TimedRun* tr, const Step& st, hipStream_t s) {
+  const ConvLaunch& L = st.L;
+  int kind = 3;
+  double mf = 0.0, macs = 0.0;   // macs: per output pixel, over the convs the step covers
+  switch (st.kind) {
+    case Step::POOL: case Step::VPOOL: case Step::POOL_DEFERRED: kind = 0; break;
+#ifdef ISLPOSE_DEV
+    case Step::WINO_X3: kind = 4; mf = wino_x3_mfma_flops(L); break;
+#endif
+    case Step::DIRECT: kind = 1; mf = conv_mfma_flops(L); break;
+    case Step::WINO: kind = 2; mf = wino_mfma_flops(L); break;
+    case Step::X3: mf = conv_x3_mfma_flops(L); break;
+    case Step::X3_RGB: mf = conv_x3_rgb_mfma_flops(L); break;
+    case Step::W2: kind = 5; mf = wino_f16_mfma_flops(L); break;
+    case Step::PAIR: mf = conv_x3_fused67_mfma_flops(L); break;
+    case Step::C12: mf = conv_x3_c12_mfma_flops(L); break;
+  }
+  for (int j = 0; j < st.nops; ++j) {
+    const Op& o = net->ops[st.op + j];
+    if (o.type != 0) continue;
+    const ConvLayer& c = net->layers[o.layer];
+    macs += (double)c.cout * c.cin * c.k * c.k;
+  }
+  for (int j = 0; j < st.nops; ++j) {
+    tr->kind.push_back(j ? 0 : kind);
+    tr->flops.push_back(j ? 0.0 : 2.0 * macs * L.H * L.W * L.n);
+    tr->mfma_flops.push_back(j ? 0.0 : mf);
+    HIP_OK(hipEventRecord(tr->ev[st.op + j + 1], s));
+  }
+  return ISL_OK;
+}
+
+// One eager run of the conv chain: the launch plan (plan_steps), issued step by step.
 static int run_ops_eager(isl_net* net, hipStream_t s) {
   isl_net::TimedRun* tr = nullptr;
   if (net->timing) {
@@ -1552,218 +1713,28 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
     HIP_OK(hipEventRecord(tr->ev[0], s));
   }
   net->op_variant.assign(net->ops.size(), 0);
-  {
-    const int rc = plan_fold(net, s);
-    if (rc) return rc;
-  }
-  const isl_net::Arena& far = *net->cur;
-  bool fused = false;   // the previous conv wrote the pair-max buffer of this pool
-  int vin_buf = -1;     // this conv stages from that buffer (the pool op was skipped)
-  const bool fuse_pools = fused_pool_enabled(), pool_input = fuse_pools && pool_input_enabled();
-  // ISL_PREC_FP16 (ISL_ALGO_X3 only): every x3 conv on the one-term form of the variant the fp32
-  // plan picks, from the hi-only packs -- the conv1_1 -> conv1_2 launch included (the same bits
-  // as its layers); the fused 1x1 pair only where ISLPOSE_X3_FUSE67 asks for it (fuse67_mode);
-  // the Winograd kernel is never chosen.
+  if (const int rc = plan_fold(net, s)) return rc;
+  isl_net::Arena& ar = *net->cur;
   const bool h16 = net->algo == ISL_ALGO_X3 && net->precision == ISL_PREC_FP16;
   if (h16 && !net->packed_hi) return fail(ISL_E_STATE, "fp16 precision: hi-only filters not uploaded");
-  // ISL_ACT_FP16: the arena of this plan holds fp16 between the convs (plan() found every conv
-  // covered); the launches below are those of the fp32-storage run, on the fp16-storage forms
-  const bool a16 = net->cur->a16;
+  // ISL_ACT_FP16: the arena of this plan holds fp16 between the convs (plan() found every step covered)
+  const bool a16 = ar.a16;
   if (a16 && !h16) return fail(ISL_E_STATE, "fp16 activation storage: the arena of this plan needs ISL_ALGO_X3 with ISL_PREC_FP16");
-  const int f67 = net->algo == ISL_ALGO_X3 ? fuse67_mode(h16) : 0;
-  size_t perm_op = (size_t)-1;   // the pair (perm_op, perm_op + 1) runs as its permuted two launches
-  for (size_t k = 0; k < net->ops.size(); ++k) {
+  std::vector<Step> steps = plan_steps(net, net->act, h16, a16, &ar);
+  for (Step& st : steps) {
+    const size_t k = st.op;
     const Op& op = net->ops[k];
-    const Act& in = net->act[op.in];
-    const Act& out = net->act[op.out];
-    const int form67 = vin_buf < 0 ? fuse67_form(net, k, f67) : 0;
-    if (form67 == 2) perm_op = k;
-    if (form67 == 1) {
-      // Mconv6 -> Mconv7 in one launch (conv_x3 VAR 16): op k's input, op k + 1's output
-      const Op& op7 = net->ops[k + 1];
-      const ConvLayer& c6 = net->layers[op.layer];
-      const ConvLayer& c7 = net->layers[op7.layer];
-      const Act& o7 = net->act[op7.out];
-      ConvLaunch L = basic_launch(net, op);
-      L.out = o7.base; L.out_pad = o7.pad; L.out_cs = o7.cs; L.out_coff = op7.out_coff;
-      L.wx3 = c6.d_wx3f ? c6.d_wx3f : c6.d_wx3;
-      L.wx3f7 = c7.d_wx3f7; L.bias7 = c7.d_b; L.slope7 = c7.d_s; L.wscale7_inv = c7.x3_inv;
-      L.cout7 = c7.cout; L.act7 = c7.act;
-      if (h16) {
-        L.f16 = 1;
-        L.wx3 = c6.d_hx3f ? c6.d_hx3f : c6.d_hx3;
-        L.wx3f7 = c7.d_hx3f7;
-      }
-      if (a16) {
-        L.act16 = 1;
-        // Mconv7 writing a net output last: the fused epilogue keeps the unrounded fp32 values too
-        for (int o = 0; o < net->n_out; ++o)
-          if ((int)k + 1 == net->out_op[o]) {
-            const Act& ob = net->act[net->out32_buf[o]];
-            L.out32 = ob.base; L.out32_pad = ob.pad; L.out32_cs = ob.cs;
-          }
-      }
-      HIP_OK(launch_conv_x3(L, s));
-      net->op_variant[k] = x3_last_variant();
-      net->op_variant[k + 1] = -2;   // ran inside op k
-      if (tr) {
-        // the pair's FLOPs and time on op k; op k + 1 an empty interval (not a launch)
-        tr->kind.push_back(3);
-        tr->flops.push_back(2.0 * in.H * in.W * in.n * ((double)c6.cout * c6.cin + (double)c7.cout * c7.cin));
-        tr->mfma_flops.push_back(conv_x3_fused67_mfma_flops(L));
-        HIP_OK(hipEventRecord(tr->ev[k + 1], s));
-        tr->kind.push_back(0); tr->flops.push_back(0.0); tr->mfma_flops.push_back(0.0);
-        HIP_OK(hipEventRecord(tr->ev[k + 2], s));
-      }
-      ++k;
-      continue;
+    ConvLaunch& L = st.L;
+    if (st.error) return fail(ISL_E_STATE, st.error);
+    if (a16 && st.kind >= Step::DIRECT) return fail(ISL_E_STATE, "fp16 activation storage: a conv off the x3 kernels");
+    if (st.late_pool >= 0) {
+      const Op& pool = net->ops[st.late_pool];
+      HIP_OK(launch_vpool2(net->act[pool.hbuf], net->act[pool.out], pool.C, s));
+      net->op_variant[st.late_pool] = 0;
     }
-
-    // conv1_1 (rgb kernel) -> conv1_2 -> pool: both convs and the pool in one launch writing the
-    // pooled map (or, ISLPOSE_C12=2, the pool's pair-max buffer), where conv1_1's output feeds
-    // conv1_2 only (conv_c12.hip)
-    ConvLaunch L1, L2;
-    const int form12 = vin_buf < 0 ? c12_form(net, k, fuse_pools, h16, a16, &L1, &L2) : 0;
-    if (form12) {
-      const Op& o2 = net->ops[k + 1];
-      const bool pool2 = form12 == 2;
-      HIP_OK(launch_conv_x3_c12(L1, L2, s));
-      // (ISL_PREC_FP16 also sets X3V_RGB: conv1_1 runs conv_x3_rgb's one-term K packing inside the
-      // launch, and the fp16 suites find the 3-channel form of a run by that bit)
-      net->op_variant[k] = x3_variant_code(X3V_C12 | (h16 ? X3V_F16 | X3V_RGB : 0) | (a16 ? X3V_A16 : 0), 3, 256, 64);
-      // conv1_2 ran inside op k.  ISL_PREC_FP16 reports it as -1, "fused with its pool": the
-      // fp16-storage suite holds every conv op of a run to the act16 bit or that code
-      net->op_variant[k + 1] = h16 ? -1 : -2;
-      if (tr) {
-        const ConvLayer& c1 = net->layers[op.layer];
-        const ConvLayer& c2 = net->layers[o2.layer];
-        tr->kind.push_back(3);
-        tr->flops.push_back(2.0 * L1.H * L1.W * L1.n * 9.0 * ((double)c1.cout * c1.cin + (double)c2.cout * c2.cin));
-        tr->mfma_flops.push_back(conv_x3_c12_mfma_flops(L1));
-        HIP_OK(hipEventRecord(tr->ev[k + 1], s));
-        tr->kind.push_back(0); tr->flops.push_back(0.0); tr->mfma_flops.push_back(0.0);
-        HIP_OK(hipEventRecord(tr->ev[k + 2], s));
-        if (pool2) {
-          tr->kind.push_back(0); tr->flops.push_back(0.0); tr->mfma_flops.push_back(0.0);
-          HIP_OK(hipEventRecord(tr->ev[k + 3], s));
-        }
-      }
-      if (pool2) {
-        net->op_variant[k + 2] = -2;   // the pool ran inside op k
-        k += 2;
-        continue;
-      }
-      fused = true;   // the pool op finds its pair-max buffer written
-      ++k;
-      continue;
-    }
-
-    if (op.type == 1) {
-      // deferred: the next conv either stages from the pair-max buffer or runs vpool2 first
-      if (fused && pool_input && pool_into_next_conv(net, k)) { vin_buf = (int)k; net->op_variant[k] = -1; }
-      else if (fused) HIP_OK(launch_vpool2(net->act[op.hbuf], out, op.C, s));
-      else HIP_OK(launch_maxpool2(in, out, op.C, s));
-      fused = false;
-      if (tr) {
-        tr->kind.push_back(0); tr->flops.push_back(0.0); tr->mfma_flops.push_back(0.0);
-        HIP_OK(hipEventRecord(tr->ev[k + 1], s));
-      }
-      continue;
-    }
-    const ConvLayer& c = net->layers[op.layer];
-    ConvLaunch L;
-    L.in = in.base; L.in_pad = in.pad; L.in_cs = in.cs; L.in_coff = op.in_coff;
-    L.out = out.base; L.out_pad = out.pad; L.out_cs = out.cs; L.out_coff = op.out_coff;
-    L.wpk = c.d_w; L.bias = c.d_b; L.slope = c.d_s;
-    L.n = in.n; L.H = in.H; L.W = in.W; L.ks = c.k; L.cin_chunks = c.cin_phys / 8;
-    L.cout = c.cout; L.bco = c.bco; L.act = c.act;
-    L.wx3 = c.d_wx3; L.wscale_inv = c.x3_inv; L.range_flag = net->d_flag;
-    int kind = 1;
-    double mf = 0.0;
-    if (net->algo == ISL_ALGO_WINO && c.wbco) {
-      L.wpk = c.d_wu; L.bco = c.wbco;
-      HIP_OK(launch_wino(L, s));
-      kind = 2; mf = wino_mfma_flops(L);
-#ifdef ISLPOSE_DEV
-    } else if (net->algo == ISL_ALGO_X3 && c.d_wux3 && x3_wino_enabled() && vin_buf < 0) {
-      L.wx3 = c.d_wux3; L.wscale_inv = c.wx3_inv;
-      HIP_OK(launch_wino_x3(L, s));
-      kind = 4; mf = wino_x3_mfma_flops(L);
-#endif
-    } else if (net->algo == ISL_ALGO_X3 && x3_fits(L)) {
-      L.allow_split = net->split_k;
-      if (vin_buf >= 0) {   // the preceding pool's row-pair max happens in this conv's staging
-        const Op& pool = net->ops[vin_buf];
-        const Act& hb = net->act[pool.hbuf];
-        ConvLaunch Lv = L;
-        Lv.in = hb.base; Lv.in_cs = hb.cs; Lv.in_coff = 0; Lv.vin = 1;
-        if (x3_vin_ok(Lv) && !(c.d_wrgb && x3_rgb_fits(L))) L = Lv;
-        else {   // no variant: the pool after all
-          HIP_OK(launch_vpool2(hb, net->act[pool.out], pool.C, s));
-          net->op_variant[vin_buf] = 0;
-        }
-        vin_buf = -1;
-      }
-      const bool perm = k == perm_op || (perm_op != (size_t)-1 && k == perm_op + 1);
-      if (perm && k == perm_op) {
-        // Mconv6 of the pair's two launches: output channels in the fused K order, its K
-        // summed in one sequence as the fused kernel does (no ranges)
-        L.wx3 = c.d_wx3p; L.bias = c.d_bp; L.slope = c.d_sp;
-        L.allow_split = 0;
-      } else if (perm) {
-        L.wx3 = c.d_wx3p;   // Mconv7 reading them through that channel map
-      } else if (c.x3_wide) {   // 256-channel tiles, two pairs per step, where the grid is big enough
-        ConvLaunch Lw = L;
-        Lw.bco = 256;
-        if (x3_wide1(Lw)) { L.bco = 256; L.wx3 = c.d_wx3w; }
-      }
-      if (h16) {
-        L.f16 = 1;
-        L.wx3 = perm ? c.d_hx3p : L.bco == 256 && c.x3_wide ? c.d_hx3w : c.d_hx3;
-      }
-      if (a16) {
-        L.act16 = 1;
-        // the layer that writes a net output last also keeps the unrounded fp32 values
-        for (int o = 0; o < net->n_out; ++o)
-          if ((int)k == net->out_op[o]) {
-            const Act& ob = net->act[net->out32_buf[o]];
-            L.out32 = ob.base; L.out32_pad = ob.pad; L.out32_cs = ob.cs;
-          }
-      }
-      // the next op pools this conv's output: write pair maxima to its half-width buffer
-      if (k + 1 < net->ops.size() && net->ops[k + 1].type == 1 && net->ops[k + 1].in == op.out && op.out_coff == 0 &&
-          net->ops[k + 1].C == c.cout && fuse_pools && x3_hpool_ok(L)) {
-        const Act& hb = net->act[net->ops[k + 1].hbuf];
-        L.out = hb.base; L.out_pad = 0; L.out_cs = hb.cs; L.out_coff = 0;
-        L.hpool = 1;
-        fused = true;
-      }
-      // the Winograd kernel: plain 3x3 launches -- no pool on either side (decided from the graph,
-      // not from whether the pool is fused, so the pool switches never change a conv's arithmetic),
-      // no fold, no K ranges
-      const bool pool_side = (k > 0 && net->ops[k - 1].type == 1 && net->ops[k - 1].out == op.in) ||
-                             (k + 1 < net->ops.size() && net->ops[k + 1].type == 1 && net->ops[k + 1].in == op.out);
-      if (!h16 && !perm && !pool_side && w2_enabled(L) && c.d_ww && !L.vin && !L.hpool && far.fold_ws_off[k] < 0 &&
-          far.fold_tab_off[k] < 0 && x3_split_ranges(L, nullptr) <= 1) {
-        ConvLaunch Lw = L;
-        Lw.wx3 = c.d_ww;
-        Lw.wscale_inv = c.ww_inv;
-        if (wino_f16_fits(Lw)) {
-          HIP_OK(launch_wino_f16(Lw, s));
-          kind = 5;   // (isl_net_timing's op kinds: 1 fp32 direct, 2 fp32 Winograd, 3 split-fp16 direct, 5 wino_f16)
-          mf = wino_f16_mfma_flops(Lw);
-          net->op_variant[k] = x3_variant_code(X3V_W2, 3, 128, 64);
-          if (tr) {
-            tr->kind.push_back(kind);
-            tr->flops.push_back(2.0 * c.cout * c.cin * c.k * c.k * (double)in.H * in.W * in.n);
-            tr->mfma_flops.push_back(mf);
-            HIP_OK(hipEventRecord(tr->ev[k + 1], s));
-          }
-          continue;
-        }
-      }
+    if (st.kind == Step::X3 || st.kind == Step::X3_RGB) {
+      // the split-K workspace and the fold pointers: allocations of this arena
       const size_t need = x3_splitk_ws_floats(L);
-      isl_net::Arena& ar = *net->cur;
       if (need > ar.ks_floats) {
         if (net->capturing) return fail(ISL_E_STATE, "graph capture: split-K workspace growth");
         drop_graphs(ar);   // they name the old workspace
@@ -1776,36 +1747,35 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
       }
       L.ws = ar.ks;
       L.ws_floats = ar.ks_floats;
-      if (far.fold_ws_off[k] >= 0) {   // a fold producer: its own partial-sum region, no reduce
-        L.ws = far.fold_mem + far.fold_ws_off[k];
+      if (ar.fold_ws_off[k] >= 0) {   // a fold producer: its own partial-sum region, no reduce
+        L.ws = ar.fold_mem + ar.fold_ws_off[k];
         L.ws_floats = need;
         L.fold_out = 1;
       }
-      if (far.fold_tab_off[k] >= 0) {   // a fold consumer
+      if (ar.fold_tab_off[k] >= 0) {   // a fold consumer
         if (L.vin || L.hpool || !x3_fold_ok(L)) return fail(ISL_E_STATE, "split-K fold: consumer off the generic loop");
-        L.fold = far.fold_tab + far.fold_tab_off[k];
+        L.fold = ar.fold_tab + ar.fold_tab_off[k];
       }
-      if (c.d_wrgb && x3_rgb_fits(L) && rgb_kernel_enabled() && !L.vin) {
-        L.wx3 = h16 ? c.d_hrgb : c.d_wrgb;
-        HIP_OK(launch_conv_x3_rgb(L, s));
-        kind = 3; mf = conv_x3_rgb_mfma_flops(L);
-      } else {
-        HIP_OK(launch_conv_x3(L, s));
-        kind = 3; mf = conv_x3_mfma_flops(L);
-      }
+    }
+    for (int j = 0; j < st.nops; ++j) net->op_variant[k + j] = st.code[j];
+    switch (st.kind) {
+      case Step::POOL: HIP_OK(launch_maxpool2(net->act[op.in], net->act[op.out], op.C, s)); break;
+      case Step::VPOOL: HIP_OK(launch_vpool2(net->act[op.hbuf], net->act[op.out], op.C, s)); break;
+      case Step::POOL_DEFERRED: break;
+      case Step::WINO: HIP_OK(launch_wino(L, s)); break;
+      case Step::W2: HIP_OK(launch_wino_f16(L, s)); break;
+      case Step::C12: HIP_OK(launch_conv_x3_c12(L, st.L2, s)); break;
+      case Step::X3_RGB: HIP_OK(launch_conv_x3_rgb(L, s)); break;
+      case Step::X3: case Step::PAIR: HIP_OK(launch_conv_x3(L, s)); break;
+      case Step::DIRECT: HIP_OK(launch_conv(L, s)); break;
+#ifdef ISLPOSE_DEV
+      case Step::WINO_X3: HIP_OK(launch_wino_x3(L, s)); break;
+#endif
+    }
+    if (st.kind == Step::X3 || st.kind == Step::X3_RGB || st.kind == Step::PAIR)
       net->op_variant[k] = x3_last_variant() | (L.fold_out ? X3V_FOLD_OUT : 0);
-    } else {
-      if (a16) return fail(ISL_E_STATE, "fp16 activation storage: a conv off the x3 kernels");
-      HIP_OK(launch_conv(L, s));
-      mf = conv_mfma_flops(L);
-    }
-    if (vin_buf >= 0) return fail(ISL_E_STATE, "pooled-input staging: the conv after a skipped pool did not take it");
-    if (tr) {
-      tr->kind.push_back(kind);
-      tr->flops.push_back(2.0 * c.cout * c.cin * c.k * c.k * (double)in.H * in.W * in.n);
-      tr->mfma_flops.push_back(mf);
-      HIP_OK(hipEventRecord(tr->ev[k + 1], s));
-    }
+    if (tr)
+      if (const int rc = record_step(net, tr, st, s)) return rc;
   }
   return ISL_OK;
 }
