@@ -306,6 +306,41 @@ int isl_body_post(isl_net* net, int n, int H, int W, int nscales, const isl_scal
 int isl_hand_post(isl_net* net, int n, int h, int w, int nscales, const isl_scale_geom* geom,
                   const float* const* d_heat, int64_t* d_peaks, void* stream);
 
+/* Run-time options of the post-processing (constants in the reference):
+ *   thre1       body peak threshold: a pixel is a peak only if the blurred map there
+ *               is > thre1 (body.py:43, used at :99-100); default 0.1
+ *   thre2       PAF sample threshold: a pair passes when more than 0.8 * mid_num of its
+ *               samples are > thre2 (body.py:44, used at :157-160); default 0.05
+ *   hand_thre   hand map threshold: binary = blurred > hand_thre (hand.py:62); default 0.05
+ *   max_people  not in the reference; 0 = no cap (default).  After the pruning of
+ *               body.py:227-231, when more than max_people subset rows remain, the
+ *               max_people rows with the largest total score (subset[:, -2]) are kept,
+ *               ties going to the lower row, in their original order.  candidate is
+ *               unchanged and ISL_E_INDEX (body.py:196) is raised as without a cap.
+ * Accepted: thre1 and hand_thre finite in [1e-30, 1e30] (an all-zero map must have an
+ * all-zero mask, and the fp32 blur filter's margins are relative to the threshold: they
+ * hold while it is a normal fp32 number), thre2 finite, max_people >= 0, reserved zero;
+ * anything else is ISL_E_ARG.  isl_post_opts_default fills in the defaults. */
+typedef struct {
+  double thre1, thre2, hand_thre;
+  int32_t max_people;
+  int32_t reserved[3];
+} isl_post_opts;
+
+int isl_post_opts_default(isl_post_opts* opts);
+
+/* isl_body_post (body.py:64-235) with thre1 (body.py:43), thre2 (body.py:44) and
+ * max_people of `opts`; NULL: the defaults, which is isl_body_post. */
+int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales, const isl_scale_geom* geom,
+                       const float* const* d_paf, const float* const* d_heat,
+                       const isl_caps* caps, void* d_result, void* stream, const isl_post_opts* opts);
+
+/* isl_hand_post (hand.py:51-74) with hand_thre of `opts` for hand.py:62's 0.05; NULL: the
+ * defaults, which is isl_hand_post. */
+int isl_hand_post_opts(isl_net* net, int n, int h, int w, int nscales, const isl_scale_geom* geom,
+                       const float* const* d_heat, int64_t* d_peaks, void* stream,
+                       const isl_post_opts* opts);
+
 /* Hand post-processing of n square crops of different sizes in one call
  * (HandEstimator.post_crops; hand.py:51-74 per crop): crop i is crop_w[i] px (host
  * array), geom[i*nscales + si] its geometry at scale si (host), its low-res maps crop
@@ -320,6 +355,12 @@ int isl_hand_post(isl_net* net, int n, int h, int w, int nscales, const isl_scal
 int isl_hand_post_crops(isl_net* net, int n, const int32_t* crop_w, int nscales,
                         const isl_scale_geom* geom, const float* const* d_heat, int64_t* d_peaks,
                         void* stream);
+
+/* isl_hand_post_crops with hand_thre of `opts` for hand.py:62's 0.05 in every crop's post;
+ * NULL: the defaults, which is isl_hand_post_crops. */
+int isl_hand_post_crops_opts(isl_net* net, int n, const int32_t* crop_w, int nscales,
+                             const isl_scale_geom* geom, const float* const* d_heat, int64_t* d_peaks,
+                             void* stream, const isl_post_opts* opts);
 
 /* Diagnostic: numpy's np.sum of a float64 array (pairwise 8192-element buffers added
  * left to right, hand.py:68's association) as the hand post computes it for component

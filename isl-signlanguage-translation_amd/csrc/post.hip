@@ -18,6 +18,8 @@
 // Every floating-point expression follows the reference's evaluation order;
 // the file is built with -ffp-contract=off so no FMA is formed.
 #include <algorithm>
+#include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <type_traits>
 #include <string>
@@ -1263,6 +1265,8 @@ struct GroupArgs {
   int* order;               // [n][max_pairs]
   unsigned char* used;      // [n][2][max_peaks]
   int limb_lds;             // large pair sets ranked in LDS (ISLPOSE_LIMB_LDS=0: the per-thread pair loop)
+  double thre2;             // isl_post_opts: a PAF sample counts when > thre2 (body.py:157-160)
+  int max_people;           // isl_post_opts: subset rows kept after the prune (0: all)
 };
 
 // One element of the two-stage resize m2(m1(low)) (body.py:68-73 then :74-76 on a frame whose
@@ -1436,7 +1440,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) l
         for (int I = 0; I < 10; ++I) {
           const double v = s_item[(q * 10 + I) * 2] + s_item[(q * 10 + I) * 2 + 1];
           sum = sum + v;                                                      // builtin sum(), left to right
-          cnt += v > 0.05;
+          cnt += v > a.thre2;
         }
         double ux, uy, nr;
         int xi, yi;
@@ -1501,7 +1505,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) l
       for (int I = 0; I < 10; ++I) {
         const double s = s_item[p * 10 + I];
         sum = sum + s;                                                        // builtin sum(), left to right
-        cnt += s > 0.05;
+        cnt += s > a.thre2;
       }
       double ux, uy, nr;
       int xi, yi;
@@ -1648,7 +1652,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) l
         point(p, I, &ux, &uy, &nr, &xi, &yi);
         const double s = paf_value(a, f, mx, yi, xi) * ux + paf_value(a, f, my, yi, xi) * uy;
         sum = sum + s;                                                        // builtin sum(), left to right
-        cnt += s > 0.05;
+        cnt += s > a.thre2;
       }
       score_of(p, sum, cnt, nr);
     }
@@ -2024,6 +2028,55 @@ __global__ void __launch_bounds__(64) assemble_kernel(GroupArgs a, int conn_cap,
       }
     }
     w += __builtin_popcountll(km);
+  }
+  // person cap (isl_post_opts.max_people; not in the reference): of the w pruned rows, now in
+  // the record, keep the max_people with the largest total score row[RW - 2], ties to the
+  // lower row, in their order.  Rank = rows that come before in that order; the row of rank
+  // max_people - 1 is the cut, and a row stays when it is at or before the cut.  (Rows are
+  // tens: every lane counts its rows' ranks over all of them.)
+  if (a.max_people > 0 && w > a.max_people) {
+    __shared__ double s_cut_score;
+    __shared__ int s_cut_row;
+    if (lane == 0) {   // (no cut when a score is NaN: no row is kept)
+      s_cut_score = INFINITY;
+      s_cut_row = -1;
+    }
+    __syncthreads();   // the prune's rows are in the record
+    for (int r = lane; r < w; r += 64) {
+      const double sr = out[(size_t)r * RW + RW - 2];
+      int rank = 0;
+      for (int j = 0; j < w; ++j) {
+        const double sj = out[(size_t)j * RW + RW - 2];
+        rank += sj > sr || (sj == sr && j < r);
+      }
+      if (rank == a.max_people - 1) {
+        s_cut_score = sr;
+        s_cut_row = r;
+      }
+    }
+    __syncthreads();
+    const double cs = s_cut_score;
+    const int cr = s_cut_row;
+    const int nrows = w;
+    w = 0;
+    for (int r0 = 0; r0 < nrows; r0 += 64) {
+      const int r = r0 + lane;
+      bool keep = false;
+      if (r < nrows) {
+        const double sr = out[(size_t)r * RW + RW - 2];
+        keep = sr > cs || (sr == cs && r <= cr);
+      }
+      // in place, in order, as the prune of the global table above
+      unsigned long long mm = __ballot(keep);
+      while (mm) {
+        const int j = __builtin_ctzll(mm);
+        mm &= mm - 1;
+        if (w != r0 + j)
+          for (int q = lane; q < RW; q += 64) out[(size_t)w * RW + q] = out[(size_t)(r0 + j) * RW + q];
+        ++w;
+        __syncthreads();
+      }
+    }
   }
   if (lane == 0) *n_rows = w;
   ASTAMP(4);
@@ -3198,11 +3251,45 @@ static void tile_prof_arm(size_t, hipStream_t) {}
 static void asm_prof_arm(size_t, hipStream_t) {}
 #endif
 
+extern "C" int isl_post_opts_default(isl_post_opts* opts) {
+  if (!opts) return post_fail(ISL_E_ARG, "isl_post_opts_default: NULL");
+  memset(opts, 0, sizeof(*opts));
+  opts->thre1 = 0.1;       // body.py:43
+  opts->thre2 = 0.05;      // body.py:44
+  opts->hand_thre = 0.05;  // hand.py:62
+  opts->max_people = 0;    // no cap
+  return ISL_OK;
+}
+
+// `opts` (NULL: the defaults) checked into `out`; the accepted ranges: include/islpose.h
+static int post_opts_resolve(const isl_post_opts* opts, isl_post_opts* out, const char* who) {
+  isl_post_opts_default(out);
+  if (!opts) return ISL_OK;
+  auto map_thre_ok = [](double t) { return std::isfinite(t) && t >= 1e-30 && t <= 1e30; };
+  if (!map_thre_ok(opts->thre1) || !map_thre_ok(opts->hand_thre) || !std::isfinite(opts->thre2) ||
+      opts->max_people < 0 || opts->reserved[0] || opts->reserved[1] || opts->reserved[2]) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s: bad isl_post_opts", who);
+    return post_fail(ISL_E_ARG, msg);
+  }
+  *out = *opts;
+  return ISL_OK;
+}
+
 extern "C" int isl_body_post(isl_net* net, int n, int H, int W, int nscales, const isl_scale_geom* geom,
                              const float* const* d_paf, const float* const* d_heat, const isl_caps* caps,
                              void* d_result, void* stream) {
+  return isl_body_post_opts(net, n, H, W, nscales, geom, d_paf, d_heat, caps, d_result, stream, nullptr);
+}
+
+extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales, const isl_scale_geom* geom,
+                                  const float* const* d_paf, const float* const* d_heat, const isl_caps* caps,
+                                  void* d_result, void* stream, const isl_post_opts* opts) {
   if (!net || n <= 0 || H <= 0 || W <= 0 || nscales <= 0 || nscales > MAX_SCALES || !geom || !caps || !d_result)
     return post_fail(ISL_E_ARG, "isl_body_post: bad argument");
+  isl_post_opts po;
+  if (int orc = post_opts_resolve(opts, &po, "isl_body_post_opts")) return orc;
+  const double thre1 = po.thre1;
   const int kind = net_kind(net);
   if (kind != ISL_BODY25 && kind != ISL_COCO) return post_fail(ISL_E_ARG, "isl_body_post needs a body net");
   PHIP(hipSetDevice(net_device(net)));
@@ -3347,7 +3434,7 @@ extern "C" int isl_body_post(isl_net* net, int n, int H, int W, int nscales, con
       if (skip2) {
         const int tx = (W + NMS_TX - 1) / NMS_TX, tyl = (H + NMS_TY - 1) / NMS_TY, nt = (int)n_tiles_all;
         hipLaunchKernelGGL(stage2_need_kernel, dim3((nt + 255) / 256), dim3(256), 0, s, fh, (const float*)bm1, H, W, tx,
-                           tyl, nt, 0.1, ty2, ry_tiles, rx_tiles, live_mid, need);
+                           tyl, nt, thre1, ty2, ry_tiles, rx_tiles, live_mid, need);
         PHIP(hipGetLastError());
       }
       if ((rc = launch_resize(fh, n, nparts, H, W, 1, div_f, heat, s, bandmax, &bm_done, need))) return rc;
@@ -3372,7 +3459,7 @@ extern "C" int isl_body_post(isl_net* net, int n, int H, int W, int nscales, con
   tile_prof_arm((size_t)gb.x * gb.y * gb.z, s);
   const int tx = (int)gb.x, tyl = (int)gb.y;
   if (multi) {
-    if ((rc = launch_blur<double, false>(gb, s, (const double*)heat, H, W, words, mask, 0.1, 0, MapSrc{}, 0, nullptr,
+    if ((rc = launch_blur<double, false>(gb, s, (const double*)heat, H, W, words, mask, thre1, 0, MapSrc{}, 0, nullptr,
                                          nullptr, tx, tyl, nullptr, amb, true)))
       return rc;
   } else if (fused) {
@@ -3383,19 +3470,19 @@ extern "C" int isl_body_post(isl_net* net, int n, int H, int W, int nscales, con
     if (wide) {
 #ifdef ISLPOSE_DEV
       hipLaunchKernelGGL((tile_live_kernel<NMS_WSRC_ROWS, NMS_WSRC_COLS>), tl, dim3(256), 0, s, fused_src, nparts, H, W,
-                         tx, tyl, n_tiles, 0.1, live, live_count);
+                         tx, tyl, n_tiles, thre1, live, live_count);
       PHIP(hipGetLastError());
       if ((rc = launch_blur<float, true, NMS_WSRC_ROWS, NMS_WSRC_COLS>(
-               dim3(std::min((n_tiles + 7) / 8 * 8, 256 * 4)), s, (const float*)nullptr, H, W, words, mask, 0.1, 0, fused_src, nparts,
+               dim3(std::min((n_tiles + 7) / 8 * 8, 256 * 4)), s, (const float*)nullptr, H, W, words, mask, thre1, 0, fused_src, nparts,
                live, live_count, tx, tyl, nullptr, amb, true)))
         return rc;
 #endif
     } else {
       hipLaunchKernelGGL((tile_live_kernel<NMS_SRC_ROWS, NMS_SRC_COLS>), tl, dim3(256), 0, s, fused_src, nparts, H, W,
-                         tx, tyl, n_tiles, 0.1, live, live_count);
+                         tx, tyl, n_tiles, thre1, live, live_count);
       PHIP(hipGetLastError());
       if ((rc = launch_blur<float, true>(dim3(std::min((n_tiles + 7) / 8 * 8, 256 * 8)), s, (const float*)nullptr, H, W, words, mask,
-                                         0.1, 0, fused_src, nparts, live, live_count, tx, tyl, nullptr, amb, true)))
+                                         thre1, 0, fused_src, nparts, live, live_count, tx, tyl, nullptr, amb, true)))
         return rc;
     }
   } else if (bm_done && band_list) {
@@ -3403,12 +3490,12 @@ extern "C" int isl_body_post(isl_net* net, int n, int H, int W, int nscales, con
     const int n_tiles = (int)(gb.x * gb.y * gb.z);
     // (mask, live_count: zeroed by init_records_kernel)
     hipLaunchKernelGGL(band_live_kernel, dim3((n_tiles + 255) / 256), dim3(256), 0, s, (const float*)bandmax, H, W,
-                       words, tx, tyl, n_tiles, 0.1, live, live_count, (const unsigned char*)live_mid);
+                       words, tx, tyl, n_tiles, thre1, live, live_count, (const unsigned char*)live_mid);
     PHIP(hipGetLastError());
     if ((rc = launch_blur<float, false>(dim3(std::min((n_tiles + 7) / 8 * 8, 256 * 8)), s, (const float*)heat, H, W, words, mask,
-                                        0.1, 0, MapSrc{}, 0, live, live_count, tx, tyl, nullptr, amb, true)))
+                                        thre1, 0, MapSrc{}, 0, live, live_count, tx, tyl, nullptr, amb, true)))
       return rc;
-  } else if ((rc = launch_blur<float, false>(gb, s, (const float*)heat, H, W, words, mask, 0.1, 0, MapSrc{}, 0, nullptr,
+  } else if ((rc = launch_blur<float, false>(gb, s, (const float*)heat, H, W, words, mask, thre1, 0, MapSrc{}, 0, nullptr,
                                              nullptr, tx, tyl, bm_done ? (const float*)bandmax : nullptr, amb, true))) {
     return rc;
   }
@@ -3440,6 +3527,8 @@ extern "C" int isl_body_post(isl_net* net, int n, int H, int W, int nscales, con
     const char* e = getenv("ISLPOSE_LIMB_LDS");
     ga.limb_lds = !(e && e[0] == '0');
   }
+  ga.thre2 = po.thre2;
+  ga.max_people = po.max_people;
   // a frame per call: the scoring over Z blocks per limb (MODE 1), then ranks and matches (MODE 2);
   // ISLPOSE_LIMB_SPLIT=0: one block per limb (A/B; read per call)
   const char* lse = getenv("ISLPOSE_LIMB_SPLIT");
@@ -3507,7 +3596,7 @@ static size_t hand_post_bytes(int n, int h, int w, int nscales, const isl_scale_
 // the kernels of one hand post (hand.py:51-74) on stream s, scratch at base
 // (hand_post_bytes); heat planes of scale si at d_heat[si] (NULL: the arena output)
 static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, const isl_scale_geom* geom,
-                            const float* const* d_heat, int64_t* d_peaks, hipStream_t s, char* base,
+                            const float* const* d_heat, int64_t* d_peaks, hipStream_t s, char* base, double thre,
                             const float* const* mid_pre = nullptr) {
   const int nparts = 21, nch = 22;
   const size_t P = (size_t)h * w;
@@ -3567,7 +3656,7 @@ static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, cons
   }
   dim3 gb((w + NMS_TX - 1) / NMS_TX, (h + NMS_TY - 1) / NMS_TY, n * nparts);
   tile_prof_arm((size_t)gb.x * gb.y * gb.z, s);
-  if (int rc = launch_blur<double, false>(gb, s, (const double*)avg, h, w, words, mask, 0.05, 1, MapSrc{}, 0, nullptr,
+  if (int rc = launch_blur<double, false>(gb, s, (const double*)avg, h, w, words, mask, thre, 1, MapSrc{}, 0, nullptr,
                                           nullptr, (int)gb.x, (int)gb.y, nullptr, amb))
     return rc;
   if (h * w <= CC_LDS_MAX) {
@@ -3605,14 +3694,22 @@ static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, cons
 
 extern "C" int isl_hand_post(isl_net* net, int n, int h, int w, int nscales, const isl_scale_geom* geom,
                              const float* const* d_heat, int64_t* d_peaks, void* stream) {
+  return isl_hand_post_opts(net, n, h, w, nscales, geom, d_heat, d_peaks, stream, nullptr);
+}
+
+extern "C" int isl_hand_post_opts(isl_net* net, int n, int h, int w, int nscales, const isl_scale_geom* geom,
+                                  const float* const* d_heat, int64_t* d_peaks, void* stream,
+                                  const isl_post_opts* opts) {
   if (!net || n <= 0 || h <= 0 || w <= 0 || nscales <= 0 || nscales > MAX_SCALES || !geom || !d_peaks)
     return post_fail(ISL_E_ARG, "isl_hand_post: bad argument");
   if (net_kind(net) != ISL_HAND) return post_fail(ISL_E_ARG, "isl_hand_post needs the hand net");
   if (nscales > 1 && !d_heat) return post_fail(ISL_E_ARG, "isl_hand_post: maps required for several scales");
+  isl_post_opts po;
+  if (int orc = post_opts_resolve(opts, &po, "isl_hand_post_opts")) return orc;
   PHIP(hipSetDevice(net_device(net)));
   char* base = (char*)net_scratch(net, hand_post_bytes(n, h, w, nscales, geom));
   if (!base) return ISL_E_HIP;
-  return hand_post_launch(net, n, h, w, nscales, geom, d_heat, d_peaks, (hipStream_t)stream, base);
+  return hand_post_launch(net, n, h, w, nscales, geom, d_heat, d_peaks, (hipStream_t)stream, base, po.hand_thre);
 }
 
 // Crops of different sizes in one call (HandEstimator.post_crops): crop i is a square of
@@ -3623,9 +3720,17 @@ extern "C" int isl_hand_post(isl_net* net, int n, int h, int w, int nscales, con
 extern "C" int isl_hand_post_crops(isl_net* net, int n, const int32_t* crop_w, int nscales,
                                    const isl_scale_geom* geom, const float* const* d_heat, int64_t* d_peaks,
                                    void* stream) {
+  return isl_hand_post_crops_opts(net, n, crop_w, nscales, geom, d_heat, d_peaks, stream, nullptr);
+}
+
+extern "C" int isl_hand_post_crops_opts(isl_net* net, int n, const int32_t* crop_w, int nscales,
+                                        const isl_scale_geom* geom, const float* const* d_heat, int64_t* d_peaks,
+                                        void* stream, const isl_post_opts* opts) {
   if (!net || n <= 0 || !crop_w || nscales <= 0 || nscales > MAX_SCALES || !geom || !d_heat || !d_peaks)
     return post_fail(ISL_E_ARG, "isl_hand_post_crops: bad argument");
   if (net_kind(net) != ISL_HAND) return post_fail(ISL_E_ARG, "isl_hand_post_crops needs the hand net");
+  isl_post_opts po;
+  if (int orc = post_opts_resolve(opts, &po, "isl_hand_post_crops_opts")) return orc;
   for (int i = 0; i < n; ++i) {
     if (crop_w[i] <= 0) return post_fail(ISL_E_ARG, "isl_hand_post_crops: bad crop size");
     for (int si = 0; si < nscales; ++si)
@@ -3708,7 +3813,7 @@ extern "C" int isl_hand_post_crops(isl_net* net, int n, const int32_t* crop_w, i
       mp[si] = mid_all[si] ? mid_all[si] + (size_t)i * 21 * g.valid_h * g.valid_w : nullptr;
     }
     const int rc = hand_post_launch(net, 1, crop_w[i], crop_w[i], nscales, geom + (size_t)i * nscales, hp,
-                                    d_peaks + (size_t)i * 42, L->stream[k], (char*)L->scratch[k], mp);
+                                    d_peaks + (size_t)i * 42, L->stream[k], (char*)L->scratch[k], po.hand_thre, mp);
     if (rc) return rc;
   }
   for (int k = 0; k < nl; ++k) {

@@ -48,13 +48,20 @@ class FrameResult:
 
 class BodyEstimator:
     def __init__(self, weights: dict = None, model_type: str = "body25", device: int = 0, scale_search=(0.5,),
-                 caps=None, net: "rt.Net" = None, precision: str = None, *, act_storage: str = None):
+                 caps=None, net: "rt.Net" = None, precision: str = None, *, act_storage: str = None,
+                 thre1: float = None, thre2: float = None, max_people: int = None):
         """precision: 'fp32' or 'fp16' (rt.Net.set_precision) for the net, or None to keep
         the net's own -- fp32 unless ISLPOSE_PRECISION=fp16 was set when it was created.
         act_storage: 'fp32' or 'fp16' (rt.Net.set_act_storage: fp16 activation buffers under
-        precision 'fp16', the same results), or None to keep the net's own."""
+        precision 'fp16', the same results), or None to keep the net's own.
+        thre1, thre2, max_people (rt.check_post_opts): the peak threshold (body.py:43, 0.1), the
+        PAF sample threshold (body.py:44, 0.05) and a cap on the persons returned (the
+        max_people best total scores after the reference's pruning, in their order; 0 or None:
+        all) of every post this estimator runs; None is the reference's constant."""
         rt.check_precision(precision)
         rt.check_act_storage(act_storage)
+        self.post_opts = rt.check_post_opts(thre1=thre1, thre2=thre2, max_people=max_people)
+        self._po = rt.post_opts_struct(self.post_opts)
         self.kind = KINDS[model_type]
         self.model_type = model_type
         self.device = device
@@ -120,7 +127,7 @@ class BodyEstimator:
 
     # -- post-processing ---------------------------------------------------------
     def post(self, n, H, W, geoms, pafs, heats, caps=None):
-        """Run isl_body_post and return the raw result records (numpy uint8) + layout."""
+        """Run isl_body_post_opts (this estimator's thre1 / thre2 / max_people) and return the raw result records (numpy uint8) + layout."""
         import torch
         caps = dict(self.caps, **(caps or {}))
         while True:
@@ -131,8 +138,8 @@ class BodyEstimator:
             g = (rt.IslScaleGeom * ns)(*[rt.IslScaleGeom(*gg) for gg in geoms])
             pp = (ctypes.c_void_p * ns)(*[rt.ptr(p).value for p in pafs])
             hp = (ctypes.c_void_p * ns)(*[rt.ptr(h).value for h in heats])
-            rt.check(rt.lib().isl_body_post(self.net.h, n, H, W, ns, g, pp, hp, ctypes.byref(c), rt.ptr(res),
-                                           rt.stream_handle()), "isl_body_post")
+            rt.check(rt.lib().isl_body_post_opts(self.net.h, n, H, W, ns, g, pp, hp, ctypes.byref(c), rt.ptr(res),
+                                                rt.stream_handle(), ctypes.byref(self._po)), "isl_body_post_opts")
             host = res.cpu().numpy()
             grow = self._grow(host, lay, n, caps)
             if grow is None:
@@ -258,8 +265,8 @@ class BodyEstimator:
             g = (rt.IslScaleGeom * ns)(*[rt.IslScaleGeom(*gg) for gg in geoms])
             pp = (ctypes.c_void_p * ns)(*[rt.ptr(p).value for p in pafs])
             hp = (ctypes.c_void_p * ns)(*[rt.ptr(h).value for h in heats])
-            rt.check(rt.lib().isl_body_post(self.net.h, n, H, W, ns, g, pp, hp, ctypes.byref(c), rt.ptr(res),
-                                           rt.stream_handle(ps)), "isl_body_post")
+            rt.check(rt.lib().isl_body_post_opts(self.net.h, n, H, W, ns, g, pp, hp, ctypes.byref(c), rt.ptr(res),
+                                                rt.stream_handle(ps), ctypes.byref(self._po)), "isl_body_post_opts")
             host = torch.empty(res.shape, dtype=torch.uint8, pin_memory=True)
             host.copy_(res, non_blocking=True)
             ev = torch.cuda.Event()

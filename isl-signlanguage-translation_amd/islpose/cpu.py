@@ -221,8 +221,23 @@ def _assemble(all_peaks, connection_all, special_k, model_type, njoint):
     return candidate, subset[keep] if len(keep) != len(subset) else subset
 
 
-def body_call(frame: np.ndarray, net_fn, model_type: str = "body25", scale_search=(0.5,)):
-    """Body.__call__ on the CPU: frame uint8 H x W x 3 (BGR); net_fn(NCHW float32) -> (paf, heat)."""
+def cap_people(subset: np.ndarray, max_people):
+    """The person cap (not in the reference; isl_post_opts.max_people): when more than
+    max_people rows remain after the pruning of body.py:227-231, the max_people rows with the
+    largest total score subset[:, -2], ties going to the lower row, in their original order.
+    0 or None: no cap."""
+    if not max_people or len(subset) <= max_people:
+        return subset
+    best = np.argsort(-subset[:, -2], kind="stable")[:max_people]   # stable: ties keep row order
+    return subset[np.sort(best)]
+
+
+def body_call(frame: np.ndarray, net_fn, model_type: str = "body25", scale_search=(0.5,), thre1=None, thre2=None,
+              max_people=None):
+    """Body.__call__ on the CPU: frame uint8 H x W x 3 (BGR); net_fn(NCHW float32) -> (paf, heat).
+    thre1 / thre2 / max_people: runtime.check_post_opts (None: body.py:43-44's 0.1 / 0.05, no cap)."""
+    from .runtime import check_post_opts
+    opts = check_post_opts(thre1=thre1, thre2=thre2, max_people=max_people)
     njoint, npaf = (26, 52) if model_type == "body25" else (19, 38)
     H, W = frame.shape[:2]
     mult = [s * BOXSIZE / H for s in scale_search]
@@ -232,9 +247,10 @@ def body_call(frame: np.ndarray, net_fn, model_type: str = "body25", scale_searc
         paf, heat = _scale_maps((H, W), frame, scale, net_fn)
         heat_avg += heat_avg + heat / len(mult)     # body.py:80 (the doubling quirk)
         paf_avg += + paf / len(mult)
-    all_peaks = _peaks(heat_avg, njoint)
-    conns, special_k = _connect(all_peaks, paf_avg, model_type, H)
-    return _assemble(all_peaks, conns, special_k, model_type, njoint)
+    all_peaks = _peaks(heat_avg, njoint, opts["thre1"])
+    conns, special_k = _connect(all_peaks, paf_avg, model_type, H, opts["thre2"])
+    candidate, subset = _assemble(all_peaks, conns, special_k, model_type, njoint)
+    return candidate, cap_people(subset, opts["max_people"])
 
 
 # ---------------------------------------------------------------------------
@@ -244,9 +260,12 @@ def body_call(frame: np.ndarray, net_fn, model_type: str = "body25", scale_searc
 HAND_SCALES = (0.5, 1.0, 1.5, 2.0)
 
 
-def hand_call(frame: np.ndarray, net_fn, scale_search=HAND_SCALES, thre=0.05):
-    """Hand.__call__ on the CPU: frame uint8 H x W x 3; net_fn(NCHW float32) -> heat [1,22,h,w]."""
+def hand_call(frame: np.ndarray, net_fn, scale_search=HAND_SCALES, thre=None):
+    """Hand.__call__ on the CPU: frame uint8 H x W x 3; net_fn(NCHW float32) -> heat [1,22,h,w].
+    thre: runtime.check_post_opts' hand_thre (None: hand.py:62's 0.05)."""
     from scipy.ndimage import gaussian_filter, label
+    from .runtime import check_post_opts
+    thre = check_post_opts(hand_thre=thre)["hand_thre"]
     H, W = frame.shape[:2]
     mult = [s * BOXSIZE / H for s in scale_search]
     heat_avg = np.zeros((H, W, 22))

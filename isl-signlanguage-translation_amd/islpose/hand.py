@@ -24,14 +24,18 @@ CROP_CHUNK = 64     # hand crops per batched pass of estimate_crops
 
 class HandEstimator:
     def __init__(self, weights: dict = None, device: int = 0, scale_search=HAND_SCALES, net: "rt.Net" = None,
-                 precision: str = None, *, act_storage: str = None):
+                 precision: str = None, *, act_storage: str = None, thre: float = None):
         """precision: 'fp32' or 'fp16' (rt.Net.set_precision) for the net, or None to keep
         the net's own -- fp32 unless ISLPOSE_PRECISION=fp16 was set when it was created.
         act_storage: 'fp32' or 'fp16' (rt.Net.set_act_storage: fp16 activation buffers under
         precision 'fp16', the same results; the small scales keep fp32 buffers), or None to keep
-        the net's own."""
+        the net's own.
+        thre (rt.check_post_opts' hand_thre): the threshold of the blurred part map (hand.py:62,
+        0.05) of every post this estimator runs; None is the reference's constant."""
         rt.check_precision(precision)
         rt.check_act_storage(act_storage)
+        self.post_opts = rt.check_post_opts(hand_thre=thre)
+        self._po = rt.post_opts_struct(self.post_opts)
         self.device = device
         self.scale_search = tuple(scale_search)
         if net is None:
@@ -76,8 +80,8 @@ class HandEstimator:
         dst = out if out is not None else torch.empty((n, 21, 2), dtype=torch.int64, device=heats[0].device)
         g = (rt.IslScaleGeom * ns)(*[rt.IslScaleGeom(*gg) for gg in geoms])
         hp = (ctypes.c_void_p * ns)(*[rt.ptr(t).value for t in heats])
-        rt.check(rt.lib().isl_hand_post(self.net.h, n, h, w, ns, g, hp, rt.ptr(dst), rt.stream_handle()),
-                 "isl_hand_post")
+        rt.check(rt.lib().isl_hand_post_opts(self.net.h, n, h, w, ns, g, hp, rt.ptr(dst), rt.stream_handle(),
+                                            ctypes.byref(self._po)), "isl_hand_post_opts")
         return None if out is not None else dst.cpu().numpy()
 
     def estimate_crops(self, frames, boxes):
@@ -178,8 +182,8 @@ class HandEstimator:
                 g[i * ns + si] = rt.IslScaleGeom(*gg)
         assert all(hh.is_contiguous() for hh in heats)
         hp = (ctypes.c_void_p * ns)(*[rt.ptr(hh).value for hh in heats])
-        rt.check(rt.lib().isl_hand_post_crops(self.net.h, n, ws, ns, g, hp, rt.ptr(out), rt.stream_handle()),
-                 "isl_hand_post_crops")
+        rt.check(rt.lib().isl_hand_post_crops_opts(self.net.h, n, ws, ns, g, hp, rt.ptr(out), rt.stream_handle(),
+                                                  ctypes.byref(self._po)), "isl_hand_post_crops_opts")
         return out
 
     def estimate(self, crops):

@@ -40,6 +40,36 @@ def check_act_storage(name):
     return name
 
 
+# post-processing options (isl_post_opts): the reference's constants and "no cap"
+POST_DEFAULTS = {"thre1": 0.1, "thre2": 0.05, "hand_thre": 0.05, "max_people": 0}
+MAP_THRE_RANGE = (1e-30, 1e30)   # accepted thre1 / hand_thre (include/islpose.h)
+
+
+def check_post_opts(thre1=None, thre2=None, hand_thre=None, max_people=None):
+    """The four post-processing options as a dict of POST_DEFAULTS' keys, a None replaced by the
+    reference's constant (max_people: 0, no cap).  ValueError for thre1 or hand_thre that is
+    not a finite number in MAP_THRE_RANGE (so not for 0, a negative or nan), thre2 not finite,
+    max_people negative or not an integer -- the checks of isl_body_post_opts."""
+    out = dict(POST_DEFAULTS)
+    for name, v in (("thre1", thre1), ("hand_thre", hand_thre)):
+        if v is None:
+            continue
+        v = float(v)
+        if not (np.isfinite(v) and MAP_THRE_RANGE[0] <= v <= MAP_THRE_RANGE[1]):
+            raise ValueError("%s must be a finite number in [%g, %g], got %r" % ((name,) + MAP_THRE_RANGE + (v,)))
+        out[name] = v
+    if thre2 is not None:
+        thre2 = float(thre2)
+        if not np.isfinite(thre2):
+            raise ValueError("thre2 must be finite, got %r" % thre2)
+        out["thre2"] = thre2
+    if max_people is not None:
+        if isinstance(max_people, bool) or int(max_people) != max_people or max_people < 0 or max_people >= 2 ** 31:
+            raise ValueError("max_people must be an integer >= 0 (0 or None: no cap), got %r" % (max_people,))
+        out["max_people"] = int(max_people)
+    return out
+
+
 LIB_PATH = os.environ.get("ISLPOSE_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "libislpose.so"))
 
 # every symbol include/islpose.h declares
@@ -51,7 +81,8 @@ EXPORTS = ["isl_abi_version", "isl_last_error", "isl_net_create", "isl_net_destr
            "isl_debug_np_sum", "isl_hand_post_crops", "isl_net_check_async", "isl_net_range_info",
            "isl_net_op_info", "isl_net_set_graph", "isl_lane_stream_create", "isl_lane_stream_destroy",
            "isl_net_set_precision", "isl_net_get_precision", "isl_net_set_act_storage",
-           "isl_net_get_act_storage", "isl_net_act_storage_active"]
+           "isl_net_get_act_storage", "isl_net_act_storage_active", "isl_post_opts_default",
+           "isl_body_post_opts", "isl_hand_post_opts", "isl_hand_post_crops_opts"]
 
 
 class IslCaps(ctypes.Structure):
@@ -71,6 +102,16 @@ class IslScaleGeom(ctypes.Structure):
 
 class IslCrop(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("frame", "x", "y", "w", "h")]
+
+
+class IslPostOpts(ctypes.Structure):
+    _fields_ = [("thre1", ctypes.c_double), ("thre2", ctypes.c_double), ("hand_thre", ctypes.c_double),
+                ("max_people", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+def post_opts_struct(opts: dict) -> IslPostOpts:
+    """check_post_opts' dict -> the isl_post_opts the *_opts entry points take."""
+    return IslPostOpts(opts["thre1"], opts["thre2"], opts["hand_thre"], opts["max_people"])
 
 
 class IslError(RuntimeError):
@@ -131,6 +172,11 @@ def lib():
     L.isl_debug_np_sum.argtypes = [vp, i64, vp, vp]
     L.isl_hand_post_crops.argtypes = [vp, i32, ctypes.POINTER(i32), i32, ctypes.POINTER(IslScaleGeom),
                                       ctypes.POINTER(vp), vp, vp]
+    po = ctypes.POINTER(IslPostOpts)
+    L.isl_post_opts_default.argtypes = [po]
+    L.isl_body_post_opts.argtypes = L.isl_body_post.argtypes + [po]
+    L.isl_hand_post_opts.argtypes = L.isl_hand_post.argtypes + [po]
+    L.isl_hand_post_crops_opts.argtypes = L.isl_hand_post_crops.argtypes + [po]
     for name in EXPORTS[2:]:
         getattr(L, name).restype = i32
     if L.isl_abi_version() != 1:

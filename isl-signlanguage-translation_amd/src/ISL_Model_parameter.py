@@ -9,6 +9,11 @@ Everything runs on the GPU through libislpose; there is no keras dependency.
 
 ``call_batch(frames)`` runs the body path for a whole batch of frames at once.
 
+``thre1``, ``thre2``, ``hand_thre``, ``max_people`` (keyword only, not in the reference): the
+post-processing options of ``Body`` and ``Hand`` (islpose.runtime.check_post_opts) for the two
+estimators this object builds; ``max_people=1`` keeps the best-scoring person, so at most two
+hand crops per frame reach the hand nets.  None is the reference's constant (no cap).
+
 ``ISLSignPosTranslator(body_model, hand_model, translation_model)`` (:308-443)
 turns a 20-frame window into [1, 20, 156] ``populate_features`` rows and applies
 ``translation_model`` -- a keras-free ``islpose.translate.SignClassifier`` (one
@@ -28,6 +33,7 @@ import numpy as np
 import torch
 import xxhash
 
+from islpose import runtime as rt
 from islpose import translate
 from islpose.body import BodyEstimator
 from islpose.hand import HandEstimator
@@ -47,7 +53,8 @@ def _as_numpy(img):
 
 
 class ISLSignPos(object):
-    def __init__(self, pt_body_model, pt_hand_model):
+    def __init__(self, pt_body_model, pt_hand_model, *, thre1=None, thre2=None, hand_thre=None, max_people=None):
+        self.post_opts = rt.check_post_opts(thre1=thre1, thre2=thre2, hand_thre=hand_thre, max_people=max_people)
         self.pt_body = pt_body_model
         self.pt_hand = pt_hand_model
         self.njoint_body = 26
@@ -70,24 +77,27 @@ class ISLSignPos(object):
         dev = self._device if self._device is not None else torch.cuda.current_device()
         bnet, hnet = self.pt_body.native(dev), self.pt_hand.native(dev)
         if self._body is None or self._body.net is not bnet:
-            self._body = BodyEstimator(model_type="body25", device=dev, scale_search=(0.5,), net=bnet)
+            self._body = BodyEstimator(model_type="body25", device=dev, scale_search=(0.5,), net=bnet,
+                                       thre1=self.post_opts["thre1"], thre2=self.post_opts["thre2"],
+                                       max_people=self.post_opts["max_people"])
             bnet.set_graph(GRAPH_REPLAY[0])
         if self._hand is None or self._hand.net is not hnet:
-            self._hand = HandEstimator(device=dev, net=hnet)
+            self._hand = HandEstimator(device=dev, net=hnet, thre=self.post_opts["hand_thre"])
             hnet.set_graph(GRAPH_REPLAY[1])
         return self._body, self._hand
 
     def state_key(self):
         """Identity of what produces the keypoints: the two modules, their current
         parameters (storage and in-place version, as _NativeNet.native() tracks them)
-        and the native nets' split-K state and precision (src.model set_precision)."""
+        and the native nets' split-K state and precision (src.model set_precision), and the
+        post-processing options (thre1, thre2, hand_thre, max_people)."""
         def part(m):
             if m is None:
                 return (None,)
             net = getattr(m, "_native_net", None)
             return (id(m), tuple((p.data_ptr(), p._version) for p in m.parameters()),
                     getattr(net, "split_k", None), getattr(m, "precision", None))
-        return part(self.pt_body) + part(self.pt_hand)
+        return part(self.pt_body) + part(self.pt_hand) + tuple(sorted(self.post_opts.items()))
 
     def bodypos(self, oriImg):
         return self._estimators()[0].estimate(np.ascontiguousarray(_as_numpy(oriImg), dtype=np.uint8))
@@ -202,8 +212,10 @@ class ISLSignPosTranslator(ISLSignPos):
 
     cache_frames = 64   # per-frame feature rows kept for overlapping windows
 
-    def __init__(self, body_model, hand_model, translation_model):
-        super().__init__(body_model, hand_model)
+    def __init__(self, body_model, hand_model, translation_model, *, thre1=None, thre2=None, hand_thre=None,
+                 max_people=None):
+        super().__init__(body_model, hand_model, thre1=thre1, thre2=thre2, hand_thre=hand_thre,
+                         max_people=max_people)
         self.model_type = 'body25'
         self.translation_layer = translation_model
         self._rows = collections.OrderedDict()

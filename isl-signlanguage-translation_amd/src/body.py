@@ -16,6 +16,13 @@ is given.
 GPU convolutions of precision 'fp16' (fp16: half the activation memory, the same results); None
 keeps the library's own (fp32 unless ISLPOSE_ACT_STORAGE=fp16 is set); an unknown value raises
 ValueError; no effect on the CPU path or under precision 'fp32'.
+``thre1``, ``thre2``, ``max_people`` (keyword only, not in the reference, on the GPU and the CPU
+path alike): the peak threshold (body.py:43, 0.1), the PAF sample threshold (body.py:44, 0.05)
+and a cap on the persons returned -- when more than ``max_people`` rows of ``subset`` remain
+after the reference's pruning, the ``max_people`` rows with the largest total score
+``subset[:, -2]`` stay (ties to the lower row, original order; ``candidate`` is unchanged).
+None is the reference's constant, and no cap (as ``max_people=0``).  ``thre1`` not a finite
+number in [1e-30, 1e30], ``thre2`` not finite or ``max_people < 0`` raises ValueError.
 ``estimate_batch(frames)`` processes a batch of frames in one pass.
 """
 from __future__ import annotations
@@ -32,9 +39,12 @@ from .model import bodypose_25_model, bodypose_model
 
 
 class Body(object):
-    def __init__(self, model_path, model_type="coco", *, precision=None, act_storage=None):
+    def __init__(self, model_path, model_type="coco", *, precision=None, act_storage=None, thre1=None, thre2=None,
+                 max_people=None):
         rt.check_precision(precision)
         rt.check_act_storage(act_storage)
+        rt.check_post_opts(thre1=thre1, thre2=thre2, max_people=max_people)
+        self.thre1, self.thre2, self.max_people = thre1, thre2, max_people
         if model_type == "coco":
             self.model, self.njoint, self.npaf = bodypose_model(), 19, 38
         elif model_type == "body25":
@@ -61,7 +71,8 @@ class Body(object):
         net = self.model.native(dev)
         kind = "body25" if self.model_type == "body25" else "coco"
         if self._est is None or self._est.net is not net or self._est.scale_search != tuple(self.scale_search):
-            self._est = BodyEstimator(model_type=kind, device=dev, scale_search=self.scale_search, net=net)
+            self._est = BodyEstimator(model_type=kind, device=dev, scale_search=self.scale_search, net=net,
+                                      thre1=self.thre1, thre2=self.thre2, max_people=self.max_people)
         return self._est
 
     def __call__(self, oriImg):
@@ -69,7 +80,8 @@ class Body(object):
         img = np.ascontiguousarray(img, dtype=np.uint8)
         if not torch.cuda.is_available():   # GPU-less host: the product's CPU path (body.py:31-32)
             return cpu.body_call(img, self._cpu_net, "body25" if self.model_type == "body25" else "coco",
-                                 tuple(self.scale_search))
+                                 tuple(self.scale_search), thre1=self.thre1, thre2=self.thre2,
+                                 max_people=self.max_people)
         return self.estimator().estimate(img)
 
     def _cpu_net(self, im):

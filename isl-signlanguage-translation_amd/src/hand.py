@@ -9,6 +9,9 @@ value raises ValueError; no effect on the CPU path, which is fp32.
 ``act_storage`` (keyword only, not in the reference): 'fp32' or 'fp16' for the buffers between the
 GPU convolutions of precision 'fp16' (the same results at half the activation memory); None keeps
 the library's own; an unknown value raises ValueError.
+``thre`` (keyword only, not in the reference, on the GPU and the CPU path alike): the threshold
+of the blurred part map (hand.py:62, 0.05); None is the reference's constant; a value that is
+not a finite number in [1e-30, 1e30] raises ValueError.
 """
 from __future__ import annotations
 
@@ -24,9 +27,11 @@ from .model import handpose_model
 
 
 class Hand(object):
-    def __init__(self, model_path, *, precision=None, act_storage=None):
+    def __init__(self, model_path, *, precision=None, act_storage=None, thre=None):
         rt.check_precision(precision)
         rt.check_act_storage(act_storage)
+        rt.check_post_opts(hand_thre=thre)
+        self.thre = thre
         self.model = handpose_model()
         if torch.cuda.is_available():
             self.model = self.model.cuda()
@@ -44,14 +49,14 @@ class Hand(object):
         dev = torch.cuda.current_device()
         net = self.model.native(dev)
         if self._est is None or self._est.net is not net:
-            self._est = HandEstimator(device=dev, net=net)
+            self._est = HandEstimator(device=dev, net=net, thre=self.thre)
         return self._est
 
     def __call__(self, oriImg):
         img = oriImg.cpu().numpy() if isinstance(oriImg, torch.Tensor) else np.asarray(oriImg)
         img = np.ascontiguousarray(img, dtype=np.uint8)
         if not torch.cuda.is_available():   # GPU-less host: the product's CPU path (hand.py:18-20)
-            return cpu.hand_call(img, self._cpu_net)
+            return cpu.hand_call(img, self._cpu_net, thre=self.thre)
         return self.estimator().estimate(img)
 
     def _cpu_net(self, im):

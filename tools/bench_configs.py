@@ -63,7 +63,7 @@ def c3(args):
     from islpose.body import BodyEstimator, scale_geometry
     from islpose.hand import HandEstimator, HAND_SCALES
     B, H, W = args.batch, 368, 656
-    body = BodyEstimator(synth.synth_weights(0), "body25", scale_search=(0.5,))
+    body = BodyEstimator(synth.synth_weights(0), "body25", scale_search=(0.5,), max_people=args.max_people)
     hand = HandEstimator(synth.synth_weights(2))
     frames = torch.from_numpy(synth.synth_frames(B, H, W, seed=5)).cuda()
     (m, nh, nw, vh, vw), = scale_geometry(H, W, (0.5,))
@@ -94,6 +94,7 @@ def c3(args):
     sec = timed(step, args.steps, args.warmup)
     gf = B * conv_gflop(0, nh, nw) + len(boxes) * sum(conv_gflop(2, s, s) for s in (184, 368, 552, 736))
     return {"config": "C3 body_25 + hand (2 crops/frame, 4 scales)", "batch": B, "crops": len(boxes),
+            "hand_crops_per_frame": round(len(boxes) / B, 2), "max_people": args.max_people,
             "frames_per_s": round(B / sec, 2), "ms_per_step": round(sec * 1e3, 2),
             "conv_gflop_per_step": round(gf, 1), "conv_tflops_fp32_equiv_wall": round(gf / sec / 1e3, 1),
             "hand_scales": list(HAND_SCALES),
@@ -149,11 +150,12 @@ def c5(args):
     wb = synth.tame_heat_layer(wb, heats[0].cpu().numpy(), "body25", gain=0.05)
     del cal
     tw = lambda d: {k: torch.from_numpy(v) for k, v in d.items()}  # noqa: E731
-    isl = ISLSignPos(Body(tw(wb), "body25").model, Hand(tw(synth.synth_weights(2))).model)
+    isl = ISLSignPos(Body(tw(wb), "body25").model, Hand(tw(synth.synth_weights(2))).model,
+                     max_people=args.max_people)
     clips = {"v%d.mp4" % k: rgb for k in range(args.c5_videos)}
     rows = [{"Filepath": f, "type": "Greetings", "expression": "hello"} for f in clips]
     res = {"config": "C5 video -> per-frame JSON, 1080x1920 RGB frames", "frames": T * len(rows),
-           "videos": len(rows), "batch": B, "export": False,
+           "videos": len(rows), "batch": B, "export": False, "max_people": args.max_people,
            "decode": "frames already decoded in host memory (pims/ffmpeg absent); the pipeline reads them as "
                      "slices of the [T,H,W,3] array"}
     for ov in ((True,) if args.c5_overlap_only else (False, True)):
@@ -197,19 +199,21 @@ def frame(args):
     wb = synth.tame_heat_layer(wb, heats[0].cpu().numpy(), "body25", gain=0.05)
     del cal
     tw = lambda d: {k: torch.from_numpy(v) for k, v in d.items()}  # noqa: E731
-    isl = ISLSignPos(Body(tw(wb), "body25").model, Hand(tw(synth.synth_weights(2))).model)
+    isl = ISLSignPos(Body(tw(wb), "body25").model, Hand(tw(synth.synth_weights(2))).model,
+                     max_people=args.max_people)
     body = isl._estimators()[0]
     for i in range(min(5, T)):          # warm-up: arenas of the body and of the hand crop sizes
         isl.call(rgb[i][:, :, ::-1])
     torch.cuda.synchronize()
-    crops, widths = 0, []
+    crops, widths, persons = 0, [], 0
     # the T frames REPEAT times over (a pass is ~0.35 s: one pass read +-4 % run to run)
     R = max(1, getattr(args, "frame_repeat", 1))
     t0 = time.perf_counter()
     for _ in range(R):
         for i in range(T):
-            _, _, hands = isl.call(rgb[i][:, :, ::-1])
+            _, sub, hands = isl.call(rgb[i][:, :, ::-1])
             crops += len(hands)
+            persons += len(sub)
     dt = (time.perf_counter() - t0) / R
     crops /= R
     t0 = time.perf_counter()
@@ -245,7 +249,8 @@ def frame(args):
             "hand_conv_launches_per_crop_4_scales": hand_launches,
             "frames": T, "passes": R, "frames_per_s": round(T / dt, 2), "ms_per_frame": round(dt / T * 1e3, 3),
             "body_ms_per_frame": round(db / T * 1e3, 3), "hand_ms_per_frame": round((dt - db) / T * 1e3, 3),
-            "hand_crops_per_frame": round(crops / T, 2),
+            "hand_crops_per_frame": round(crops / T, 2), "persons_per_frame": round(persons / R / T, 2),
+            "max_people": args.max_people,
             "crop_width_px": [int(min(widths)), int(max(widths))] if widths else [],
             "basis": "wall time of T sequential calls (host frame -> pinned H2D -> GPU flip -> body net + post -> "
                      "handDetect -> hand crops batched per scale -> peaks on the host); body = upload + estimate + "
@@ -309,6 +314,9 @@ def main():
                     help="storage of the activations between the fp16-precision convs of every net "
                          "(rt.Net.set_act_storage): fp16 halves the activation buffers at the same bits; "
                          "default: the library's (env ISLPOSE_ACT_STORAGE)")
+    ap.add_argument("--max-people", type=int, default=None,
+                    help="FRAME / C3 / C5: keep the N best-scoring persons of a frame (ISLSignPos / BodyEstimator "
+                         "max_people; 1: the signer only, at most two hand crops per frame); default: no cap")
     a = ap.parse_args()
     if a.precision:
         os.environ["ISLPOSE_PRECISION"] = a.precision   # read by every net at its creation

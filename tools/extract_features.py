@@ -42,6 +42,12 @@ def main():
                     help="precision of the body and hand nets' convolutions (Body / Hand precision=): fp16 = one "
                          "fp16 product per multiply-add instead of three, faster, ~2e-3 of the maps' maximum in "
                          "error; default: the library's (fp32 unless ISLPOSE_PRECISION=fp16)")
+    ap.add_argument("--thre1", type=float, default=None, help="body peak threshold (body.py:43; default 0.1)")
+    ap.add_argument("--thre2", type=float, default=None, help="PAF sample threshold (body.py:44; default 0.05)")
+    ap.add_argument("--hand-thre", type=float, default=None, help="hand map threshold (hand.py:62; default 0.05)")
+    ap.add_argument("--max-people", type=int, default=None,
+                    help="keep the N best-scoring persons of a frame (1: the signer only, at most two hand "
+                         "crops per frame); default: no cap")
     a = ap.parse_args()
 
     import torch
@@ -67,7 +73,8 @@ def main():
 
     body = Body(weights(a.body_weights, 0), "body25", precision=a.precision)
     hand = Hand(weights(a.hand_weights, 2), precision=a.precision)
-    model = ISLSignPos(body.model, hand.model)
+    model = ISLSignPos(body.model, hand.model, thre1=a.thre1, thre2=a.thre2, hand_thre=a.hand_thre,
+                       max_people=a.max_people)
 
     if a.synthetic:
         T, H, W = (int(v) for v in a.synthetic.split(","))
