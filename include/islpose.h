@@ -137,6 +137,18 @@ int isl_net_preprocess_crops(isl_net* net, const uint8_t* d_frames, int n_frames
                              const isl_crop* crops, int n_crops, double scale_times_box, int* net_h,
                              int* net_w, void* stream);
 
+/* isl_net_preprocess_crops with a left-right mirror per crop (not in the reference, which
+ * inherited pytorch-openpose's omission of OpenPose's left-hand mirroring): `flip` is a host
+ * array of n_crops flags, NULL for none.  Crop i with flip[i] != 0 fills its slot with exactly
+ * what isl_net_preprocess_crops writes for the contiguous image crop[:, ::-1]: the kernel reads
+ * source column sw - 1 - xi for every column xi it would read, in the cubic and the identity
+ * path; everything indexed by the output column (OpenCV's SIMD-body / scalar-tail split of a
+ * row, the pad) is unchanged -- the resize of a mirrored crop is not the mirror of the resize.
+ * flip == NULL is isl_net_preprocess_crops. */
+int isl_net_preprocess_crops_flip(isl_net* net, const uint8_t* d_frames, int n_frames, int H, int W,
+                                  const isl_crop* crops, const uint8_t* flip, int n_crops,
+                                  double scale_times_box, int* net_h, int* net_w, void* stream);
+
 /* Run the network on the input buffer filled by isl_net_preprocess; outputs stay
  * in the arena (low-res, 8-channel chunks) for the post kernels, and are also
  * copied to d_out0/d_out1 (NCHW) when those are non-NULL. */
@@ -361,6 +373,25 @@ int isl_hand_post_crops(isl_net* net, int n, const int32_t* crop_w, int nscales,
 int isl_hand_post_crops_opts(isl_net* net, int n, const int32_t* crop_w, int nscales,
                              const isl_scale_geom* geom, const float* const* d_heat, int64_t* d_peaks,
                              void* stream, const isl_post_opts* opts);
+
+/* isl_hand_post_opts / isl_hand_post_crops_opts with two more arguments (not in the reference):
+ *   flip      host array, one flag per crop, NULL for none: crop i's maps are those of the
+ *             mirrored crop (isl_net_preprocess_crops_flip).  The whole post runs unchanged in
+ *             the coordinates of the image the net saw; only the final store mirrors the x of
+ *             a detected part back into the caller's crop: x -> w - 1 - x.
+ *   d_scores  device double [n][21], NULL for not wanted: for a part whose thresholded map is
+ *             not empty (np.sum(binary) != 0, hand.py:63) the value of map_ori at the returned
+ *             pixel after hand.py:70's masking -- the scale-averaged map there, which OpenPose
+ *             reports as the keypoint's confidence; for an empty part 0.0.
+ * An empty part stays [0, 0] with score 0.0, mirrored or not, so a score > 0 tells "found at
+ * the origin" from "nothing found".  Both NULL: the _opts entry points. */
+int isl_hand_post_ex(isl_net* net, int n, int h, int w, int nscales, const isl_scale_geom* geom,
+                     const float* const* d_heat, int64_t* d_peaks, void* stream,
+                     const isl_post_opts* opts, const uint8_t* flip, double* d_scores);
+int isl_hand_post_crops_ex(isl_net* net, int n, const int32_t* crop_w, int nscales,
+                           const isl_scale_geom* geom, const float* const* d_heat, int64_t* d_peaks,
+                           void* stream, const isl_post_opts* opts, const uint8_t* flip,
+                           double* d_scores);
 
 /* Diagnostic: numpy's np.sum of a float64 array (pairwise 8192-element buffers added
  * left to right, hand.py:68's association) as the hand post computes it for component

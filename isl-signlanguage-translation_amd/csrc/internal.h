@@ -215,7 +215,7 @@ hipError_t launch_unpack_nchw(const Act& in, int coff, int C, float* y, hipStrea
 hipError_t launch_preprocess_tab(const uint8_t* frames, long long row_bytes, const void* d_tab, int n,
                                  const Act& out, hipStream_t s);
 size_t preprocess_entry_bytes();
-void preprocess_entry(void* dst, long long off, int sh, int sw, int rh, int rw, double scale);
+void preprocess_entry(void* dst, long long off, int sh, int sw, int rh, int rw, double scale, int flip = 0);
 
 struct MapSrc {            // one single-stage cubic resize, sampled per output element
   const float* base;       // element (f, c, y, x) at base + f*fs + chan(c) + y*ys + x*xs,

@@ -228,6 +228,8 @@ struct PreSrc {
   int sh, sw;          // image size
   int rh, rw;          // resized size (cvRound(s * fx)); the rest of the net input is pad 128
   double scale;        // source pixels per output pixel (1 / fx)
+  int flip;            // != 0: the image is this one mirrored left to right (img[:, ::-1])
+  int reserved;        // zero (the table is compared bytewise, upload_tab)
 };
 
 // `tab` (device) describes image f = blockIdx.y; `row` = bytes per source row (frame W * 3).
@@ -239,19 +241,26 @@ __global__ void preprocess_kernel(const uint8_t* __restrict__ frames, const PreS
   const int body = rowlen - rowlen % 8;
   const bool identity = t.rh == t.sh && t.rw == t.sw;
   const uint8_t* img = frames + t.off;
+  // a mirrored image: source column xi is column sw - 1 - xi of the stored one; everything
+  // indexed by the output column (the float / fixed split, the pad) is as without the mirror
+  const bool flip = t.flip != 0;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ph * pw; i += gridDim.x * blockDim.x) {
     const int y = i / pw, x = i - y * pw;
     float v[3];
     if (y >= t.rh || x >= t.rw) {
       v[0] = v[1] = v[2] = 128.f / 256.f - 0.5f;
     } else if (identity) {
-      const uint8_t* p = img + (size_t)y * row + (size_t)x * 3;
+      const uint8_t* p = img + (size_t)y * row + (size_t)(flip ? t.sw - 1 - x : x) * 3;
       for (int c = 0; c < 3; ++c) v[c] = (float)p[c] / 256.f - 0.5f;
     } else {
       int xi[4], yi[4];
       float xc[4], yc[4];
       axis_tap(x, t.scale, t.sw, xi, xc);
       axis_tap(y, t.scale, t.sh, yi, yc);
+      if (flip) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) xi[k] = t.sw - 1 - xi[k];
+      }
       int ia[4], ib[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -301,9 +310,10 @@ hipError_t launch_preprocess_tab(const uint8_t* frames, long long row_bytes, con
 
 size_t preprocess_entry_bytes() { return sizeof(PreSrc); }
 
-void preprocess_entry(void* dst, long long off, int sh, int sw, int rh, int rw, double scale) {
+void preprocess_entry(void* dst, long long off, int sh, int sw, int rh, int rw, double scale, int flip) {
   PreSrc t;
   t.off = off; t.sh = sh; t.sw = sw; t.rh = rh; t.rw = rw; t.scale = scale;
+  t.flip = flip != 0; t.reserved = 0;
   memcpy(dst, &t, sizeof(t));
 }
 

@@ -2756,7 +2756,8 @@ __device__ __forceinline__ void cc_pick(double& v, int& i, double v2, int i2) {
   if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
 }
 
-__device__ __forceinline__ int cc_block_argmax(double v, int i, double* s_d, int* s_i) {
+// *best_v (when wanted) receives the value reduced alongside the index
+__device__ __forceinline__ int cc_block_argmax(double v, int i, double* s_d, int* s_i, double* best_v = nullptr) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) cc_pick(v, i, __shfl_xor(v, o, 64), __shfl_xor(i, o, 64));
   if ((threadIdx.x & 63) == 0) { s_d[threadIdx.x >> 6] = v; s_i[threadIdx.x >> 6] = i; }
@@ -2766,7 +2767,30 @@ __device__ __forceinline__ int cc_block_argmax(double v, int i, double* s_d, int
 #pragma unroll
   for (int k = 1; k < CC_NW; ++k) cc_pick(bv, bi, s_d[k], s_i[k]);
   __syncthreads();
+  if (best_v) *best_v = bv;
   return bi;
+}
+
+// Per-crop mirror flags of one hand_cc_kernel launch (isl_hand_post_ex): bit c of the launch's
+// crop c (blockIdx.x / 21), passed by value -- no table to upload.  A larger batch is launched
+// in groups of CC_FLIP_CROPS crops.
+constexpr int CC_FLIP_CROPS = 256;
+struct CcFlip {
+  unsigned long long bits[CC_FLIP_CROPS / 64];
+};
+
+// The one store of hand_cc_kernel's three exits (thread 0 only).  found: the thresholded map
+// is not empty (hand.py:63); p = the chosen pixel, v = the masked map_ori there (hand.py:70-71),
+// which is the keypoint's score.  A mirrored crop (the net saw crop[:, ::-1]) reports x in the
+// caller's crop: w - 1 - x.  Nothing found: [0, 0] and score 0.0, mirrored or not.
+__device__ __forceinline__ void cc_store(long long* __restrict__ out, double* __restrict__ scores, int plane, bool found,
+                                         int p, double v, int w, bool flip) {
+  const int y = found ? p / w : 0;
+  int x = found ? p - y * w : 0;
+  if (found && flip) x = w - 1 - x;
+  out[plane * 2] = x;       // [x, y]
+  out[plane * 2 + 1] = y;
+  if (scores) scores[plane] = found ? v : 0.0;
 }
 
 // inclusive prefix sum of v over the CC_NT-thread block; total = the block's sum
@@ -2835,9 +2859,12 @@ __global__ void __launch_bounds__(CC_NT) hand_cc_kernel(const double* __restrict
                                                         double* __restrict__ vals_all, const CcStats* __restrict__ stats,
                                                         const CcChunk* __restrict__ ck, int chunks,
                                                         long long* __restrict__ out,
-                                                        const double* __restrict__ bsum_all, int maxb) {
+                                                        const double* __restrict__ bsum_all, int maxb, int plane0,
+                                                        CcFlip flips, double* __restrict__ scores) {
   extern __shared__ int s_dyn[];
-  const int plane = blockIdx.x;   // crop * 21 + part
+  const int plane = plane0 + blockIdx.x;   // crop * 21 + part
+  const int fc = blockIdx.x / 21;          // the crop's place in this launch's flags
+  const bool flip = (flips.bits[fc >> 6] >> (fc & 63)) & 1ull;
   const int P = h * w, tid = threadIdx.x;
   const double* map = planes + (size_t)plane * P;
   const unsigned long long* mk = mask + (size_t)plane * h * words;
@@ -2871,7 +2898,7 @@ __global__ void __launch_bounds__(CC_NT) hand_cc_kernel(const double* __restrict
     }
   }
   if (cc_block_sum(local, s_i) == 0) {     // np.sum(binary) == 0 -> [0, 0]
-    if (tid == 0) { out[plane * 2] = 0; out[plane * 2 + 1] = 0; }
+    if (tid == 0) cc_store(out, scores, plane, false, 0, 0.0, w, flip);
     return;
   }
   if constexpr (PRE) {
@@ -2905,11 +2932,9 @@ __global__ void __launch_bounds__(CC_NT) hand_cc_kernel(const double* __restrict
       int bi = 0x7fffffff;
       for (int c = tid; c < chunks; c += CC_NT)
         if (pc[c].count[bestk] > 0) cc_pick(bv, bi, pc[c].bestv[bestk], pc[c].besti[bestk]);
-      const int pbest = cc_block_argmax(bv, bi, s_d, s_i);
-      if (tid == 0) {
-        out[plane * 2] = pbest % w;
-        out[plane * 2 + 1] = pbest / w;
-      }
+      double vbest;
+      const int pbest = cc_block_argmax(bv, bi, s_d, s_i, &vbest);
+      if (tid == 0) cc_store(out, scores, plane, true, pbest, vbest, w, flip);
       return;
     }
   }
@@ -3035,11 +3060,9 @@ __global__ void __launch_bounds__(CC_NT) hand_cc_kernel(const double* __restrict
       if (p < P) cc_pick(bv, bi, parent[p] == best ? map[p] : 0.0, p);
     }
   }
-  const int pbest = cc_block_argmax(bv, bi, s_d, s_i);
-  if (tid == 0) {
-    out[plane * 2] = pbest % w;       // [x, y]
-    out[plane * 2 + 1] = pbest / w;
-  }
+  double vbest;
+  const int pbest = cc_block_argmax(bv, bi, s_d, s_i, &vbest);
+  if (tid == 0) cc_store(out, scores, plane, true, pbest, vbest, w, flip);
 }
 
 // (also zeroes the post's two list counters z0, z1, z16 16-byte words at zb and y16 at yb -- one
@@ -3597,7 +3620,8 @@ static size_t hand_post_bytes(int n, int h, int w, int nscales, const isl_scale_
 // (hand_post_bytes); heat planes of scale si at d_heat[si] (NULL: the arena output)
 static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, const isl_scale_geom* geom,
                             const float* const* d_heat, int64_t* d_peaks, hipStream_t s, char* base, double thre,
-                            const float* const* mid_pre = nullptr) {
+                            const float* const* mid_pre = nullptr, const uint8_t* flip = nullptr,
+                            double* d_scores = nullptr) {
   const int nparts = 21, nch = 22;
   const size_t P = (size_t)h * w;
   const int words = (w + 63) / 64;
@@ -3659,6 +3683,13 @@ static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, cons
   if (int rc = launch_blur<double, false>(gb, s, (const double*)avg, h, w, words, mask, thre, 1, MapSrc{}, 0, nullptr,
                                           nullptr, (int)gb.x, (int)gb.y, nullptr, amb))
     return rc;
+  // the last kernel, in groups of CC_FLIP_CROPS crops whose mirror flags ride in the launch
+  auto flips_of = [&](int c0, int nc) {
+    CcFlip f = {};
+    for (int c = 0; flip && c < nc; ++c)
+      if (flip[c0 + c]) f.bits[c >> 6] |= 1ull << (c & 63);
+    return f;
+  };
   if (h * w <= CC_LDS_MAX) {
     static bool attr = false;
     if (!attr) {
@@ -3666,9 +3697,12 @@ static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, cons
                                CC_LDS_MAX * 4));
       attr = true;
     }
-    hipLaunchKernelGGL((hand_cc_kernel<true, false>), dim3(n * nparts), dim3(CC_NT), (size_t)h * w * 4, s,
-                       (const double*)avg, mask, h, w, words, parent, vals, nullptr, nullptr, 0, (long long*)d_peaks,
-                       nullptr, 0);
+    for (int c0 = 0; c0 < n; c0 += CC_FLIP_CROPS) {
+      const int nc = std::min(n - c0, CC_FLIP_CROPS);
+      hipLaunchKernelGGL((hand_cc_kernel<true, false>), dim3(nc * nparts), dim3(CC_NT), (size_t)h * w * 4, s,
+                         (const double*)avg, mask, h, w, words, parent, vals, nullptr, nullptr, 0, (long long*)d_peaks,
+                         nullptr, 0, c0 * nparts, flips_of(c0, nc), d_scores);
+    }
   } else {
     if (w > CC_WMAX) return post_fail(ISL_E_ARG, "isl_hand_post: crop wider than 8192 px");
     const int rows = cc_rows, chunks = cc_chunks;
@@ -3685,8 +3719,12 @@ static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, cons
     const int maxb = (int)(P / 8192) + 1;
     hipLaunchKernelGGL(cc_bufsum_kernel, dim3(n * nparts, std::max(1, std::min(32, (maxb + 3) / 4))), dim3(256), 0, s,
                        stats, cks, chunks, (int)P, vals, bsum, maxb);
-    hipLaunchKernelGGL((hand_cc_kernel<false, true>), dim3(n * nparts), dim3(CC_NT), 0, s, (const double*)avg, mask,
-                       h, w, words, parent, vals, stats, cks, chunks, (long long*)d_peaks, bsum, maxb);
+    for (int c0 = 0; c0 < n; c0 += CC_FLIP_CROPS) {
+      const int nc = std::min(n - c0, CC_FLIP_CROPS);
+      hipLaunchKernelGGL((hand_cc_kernel<false, true>), dim3(nc * nparts), dim3(CC_NT), 0, s, (const double*)avg, mask,
+                         h, w, words, parent, vals, stats, cks, chunks, (long long*)d_peaks, bsum, maxb, c0 * nparts,
+                         flips_of(c0, nc), d_scores);
+    }
   }
   PHIP(hipGetLastError());
   return ISL_OK;
@@ -3700,6 +3738,12 @@ extern "C" int isl_hand_post(isl_net* net, int n, int h, int w, int nscales, con
 extern "C" int isl_hand_post_opts(isl_net* net, int n, int h, int w, int nscales, const isl_scale_geom* geom,
                                   const float* const* d_heat, int64_t* d_peaks, void* stream,
                                   const isl_post_opts* opts) {
+  return isl_hand_post_ex(net, n, h, w, nscales, geom, d_heat, d_peaks, stream, opts, nullptr, nullptr);
+}
+
+extern "C" int isl_hand_post_ex(isl_net* net, int n, int h, int w, int nscales, const isl_scale_geom* geom,
+                                const float* const* d_heat, int64_t* d_peaks, void* stream,
+                                const isl_post_opts* opts, const uint8_t* flip, double* d_scores) {
   if (!net || n <= 0 || h <= 0 || w <= 0 || nscales <= 0 || nscales > MAX_SCALES || !geom || !d_peaks)
     return post_fail(ISL_E_ARG, "isl_hand_post: bad argument");
   if (net_kind(net) != ISL_HAND) return post_fail(ISL_E_ARG, "isl_hand_post needs the hand net");
@@ -3709,7 +3753,8 @@ extern "C" int isl_hand_post_opts(isl_net* net, int n, int h, int w, int nscales
   PHIP(hipSetDevice(net_device(net)));
   char* base = (char*)net_scratch(net, hand_post_bytes(n, h, w, nscales, geom));
   if (!base) return ISL_E_HIP;
-  return hand_post_launch(net, n, h, w, nscales, geom, d_heat, d_peaks, (hipStream_t)stream, base, po.hand_thre);
+  return hand_post_launch(net, n, h, w, nscales, geom, d_heat, d_peaks, (hipStream_t)stream, base, po.hand_thre,
+                          nullptr, flip, d_scores);
 }
 
 // Crops of different sizes in one call (HandEstimator.post_crops): crop i is a square of
@@ -3726,6 +3771,13 @@ extern "C" int isl_hand_post_crops(isl_net* net, int n, const int32_t* crop_w, i
 extern "C" int isl_hand_post_crops_opts(isl_net* net, int n, const int32_t* crop_w, int nscales,
                                         const isl_scale_geom* geom, const float* const* d_heat, int64_t* d_peaks,
                                         void* stream, const isl_post_opts* opts) {
+  return isl_hand_post_crops_ex(net, n, crop_w, nscales, geom, d_heat, d_peaks, stream, opts, nullptr, nullptr);
+}
+
+extern "C" int isl_hand_post_crops_ex(isl_net* net, int n, const int32_t* crop_w, int nscales,
+                                      const isl_scale_geom* geom, const float* const* d_heat, int64_t* d_peaks,
+                                      void* stream, const isl_post_opts* opts, const uint8_t* flip,
+                                      double* d_scores) {
   if (!net || n <= 0 || !crop_w || nscales <= 0 || nscales > MAX_SCALES || !geom || !d_heat || !d_peaks)
     return post_fail(ISL_E_ARG, "isl_hand_post_crops: bad argument");
   if (net_kind(net) != ISL_HAND) return post_fail(ISL_E_ARG, "isl_hand_post_crops needs the hand net");
@@ -3813,7 +3865,8 @@ extern "C" int isl_hand_post_crops_opts(isl_net* net, int n, const int32_t* crop
       mp[si] = mid_all[si] ? mid_all[si] + (size_t)i * 21 * g.valid_h * g.valid_w : nullptr;
     }
     const int rc = hand_post_launch(net, 1, crop_w[i], crop_w[i], nscales, geom + (size_t)i * nscales, hp,
-                                    d_peaks + (size_t)i * 42, L->stream[k], (char*)L->scratch[k], po.hand_thre, mp);
+                                    d_peaks + (size_t)i * 42, L->stream[k], (char*)L->scratch[k], po.hand_thre, mp,
+                                    flip ? flip + i : nullptr, d_scores ? d_scores + (size_t)i * 21 : nullptr);
     if (rc) return rc;
   }
   for (int k = 0; k < nl; ++k) {

@@ -2229,6 +2229,13 @@ int isl_net_preprocess(isl_net* net, const uint8_t* d_frames, int n, int H, int 
 int isl_net_preprocess_crops(isl_net* net, const uint8_t* d_frames, int n_frames, int H, int W,
                              const isl_crop* crops, int n_crops, double scale_times_box, int* net_h, int* net_w,
                              void* stream) {
+  return isl_net_preprocess_crops_flip(net, d_frames, n_frames, H, W, crops, nullptr, n_crops, scale_times_box, net_h,
+                                       net_w, stream);
+}
+
+int isl_net_preprocess_crops_flip(isl_net* net, const uint8_t* d_frames, int n_frames, int H, int W,
+                                  const isl_crop* crops, const uint8_t* flip, int n_crops, double scale_times_box,
+                                  int* net_h, int* net_w, void* stream) {
   if (!net || !d_frames || !crops || n_frames <= 0 || n_crops <= 0 || H <= 0 || W <= 0 || !(scale_times_box > 0))
     return fail(ISL_E_ARG, "bad argument");
   const size_t eb = preprocess_entry_bytes();
@@ -2247,7 +2254,7 @@ int isl_net_preprocess_crops(isl_net* net, const uint8_t* d_frames, int n_frames
     if (i == 0) { ph = h8; pw = w8; }
     if (h8 != ph || w8 != pw) return fail(ISL_E_ARG, "crops resize to different net sizes: batch them separately");
     const long long off = (((long long)c.frame * H + c.y) * W + c.x) * 3;
-    preprocess_entry(net->h_tab.data() + eb * i, off, c.h, c.w, rh, rw, 1.0 / m);
+    preprocess_entry(net->h_tab.data() + eb * i, off, c.h, c.w, rh, rw, 1.0 / m, flip && flip[i]);
   }
   int rc = prepare(net);
   if (rc) return rc;

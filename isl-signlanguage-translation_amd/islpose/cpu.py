@@ -260,27 +260,39 @@ def body_call(frame: np.ndarray, net_fn, model_type: str = "body25", scale_searc
 HAND_SCALES = (0.5, 1.0, 1.5, 2.0)
 
 
-def hand_call(frame: np.ndarray, net_fn, scale_search=HAND_SCALES, thre=None):
+def hand_call(frame: np.ndarray, net_fn, scale_search=HAND_SCALES, thre=None, flip=False, return_scores=False):
     """Hand.__call__ on the CPU: frame uint8 H x W x 3; net_fn(NCHW float32) -> heat [1,22,h,w].
-    thre: runtime.check_post_opts' hand_thre (None: hand.py:62's 0.05)."""
+    thre: runtime.check_post_opts' hand_thre (None: hand.py:62's 0.05).
+    scale_search: runtime.check_hand_opts' hand_scales (None: hand.py:25's pyramid).
+    flip (not in the reference): run on frame[:, ::-1] and report the detected keypoints in the
+    frame given, x -> W - 1 - x; a part that was not found stays [0, 0].
+    return_scores (not in the reference): -> (peaks, scores float64 [21]), the masked map_ori at
+    the returned pixel (hand.py:70-71), 0.0 for a part that was not found."""
     from scipy.ndimage import gaussian_filter, label
-    from .runtime import check_post_opts
+    from .runtime import check_hand_opts, check_post_opts
     thre = check_post_opts(hand_thre=thre)["hand_thre"]
+    scale_search = check_hand_opts(hand_scales=scale_search)["hand_scales"]
+    if flip:
+        frame = np.ascontiguousarray(frame[:, ::-1])
     H, W = frame.shape[:2]
     mult = [s * BOXSIZE / H for s in scale_search]
     heat_avg = np.zeros((H, W, 22))
     for scale in mult:
         heat_avg += _scale_maps((H, W), frame, scale, net_fn)[0] / len(mult)
-    peaks = []
+    peaks, scores = [], []
     for part in range(21):
         map_ori = heat_avg[:, :, part]
         binary = gaussian_filter(map_ori, sigma=3) > thre
         if not binary.any():
             peaks.append([0, 0])
+            scores.append(0.0)
             continue
         lab, n = label(binary, structure=np.ones((3, 3), np.int32))   # 8-connected, raster-order labels
         best = int(np.argmax([np.sum(map_ori[lab == i]) for i in range(1, n + 1)])) + 1
         m = np.where(lab == best, map_ori, 0.0)
         i = int(m.max(1).argmax())            # util.npmax: row of the first maximal row maximum
-        peaks.append([int(m[i].argmax()), i])
-    return np.array(peaks)
+        x = int(m[i].argmax())
+        peaks.append([W - 1 - x if flip else x, i])
+        scores.append(float(m[i, x]))
+    peaks = np.array(peaks)
+    return (peaks, np.array(scores, np.float64)) if return_scores else peaks

@@ -36,13 +36,21 @@ import numpy as np
 from .parallel import gather_to_rank0, shard_bounds
 
 
-def frame_json(candidate, subset, all_hand_peaks) -> str:
-    """The reference's per-frame JSON text (extract_features_mp.py:79-84)."""
-    return json.dumps({
+def frame_json(candidate, subset, all_hand_peaks, hand_info=None) -> str:
+    """The reference's per-frame JSON text (extract_features_mp.py:79-84).  hand_info (the
+    fourth item of an ISLSignPos(hand_info=True) result; not in the reference) adds a
+    'hand_info' key: per hand {'person', 'is_left', 'box': [x, y, w], 'scores': [21 floats]};
+    without it the text is the reference's, byte for byte."""
+    d = {
         'candidate': np.asarray(candidate).tolist(),
         'subset': np.asarray(subset).tolist(),
         'all_hand_peaks': [np.asarray(p).tolist() for p in all_hand_peaks],
-    })
+    }
+    if hand_info is not None:
+        d['hand_info'] = [{'person': int(h['person']), 'is_left': bool(h['is_left']),
+                           'box': [int(v) for v in h['box']], 'scores': np.asarray(h['scores']).tolist()}
+                          for h in hand_info]
+    return json.dumps(d)
 
 
 def json_path(out_base: str, label_type: str, expression: str, filename: str, idx: int,
@@ -58,7 +66,7 @@ def feature_row(path: str, idx: int, label_type: str, expression: str, feature, 
     get_handpose export has two hand slots, so a frame with more than two hands
     raises IndexError there, as in the reference; export=False leaves the four
     export columns out."""
-    candidate, subset, hands = feature
+    candidate, subset, hands = feature[:3]     # (a fourth item: ISLSignPos' hand_info, JSON only)
     row = {
         'transform': transform, 'filepath': path, 'frame_no': idx, 'type': label_type,
         'expression': expression, 'candidate': np.asarray(candidate).tolist(),

@@ -70,6 +70,48 @@ def check_post_opts(thre1=None, thre2=None, hand_thre=None, max_people=None):
     return out
 
 
+HAND_SCALES = (0.5, 1.0, 1.5, 2.0)   # Hand.__call__'s pyramid (hand.py:25)
+MAX_HAND_SCALES = 8                  # MAX_SCALES of the post kernels
+HAND_BOXSIZE = 368                   # hand.py:26
+MIN_HAND_SCALE_PX = 8                # one stride-8 cell of the hand net
+
+
+def check_hand_opts(hand_scales=None, flip_left=False):
+    """The hand-path options as a dict(hand_scales=tuple of floats, flip_left=bool).
+    hand_scales: the pyramid of Hand.__call__ (hand.py:25), None for the reference's
+    (0.5, 1.0, 1.5, 2.0); 1 to MAX_HAND_SCALES entries, each a finite number > 0 whose
+    round(s * 368) is at least 8 px.  flip_left: mirror left-hand crops before the net and the
+    keypoints back after it (OpenPose's own hand extractor; not in the reference).  ValueError
+    for anything else, with or without a GPU."""
+    if hand_scales is None:
+        scales = HAND_SCALES
+    else:
+        try:
+            scales = tuple(float(s) for s in hand_scales)
+        except TypeError:
+            raise ValueError("hand_scales must be a sequence of numbers, got %r" % (hand_scales,))
+        if not 1 <= len(scales) <= MAX_HAND_SCALES:
+            raise ValueError("hand_scales needs 1 to %d entries, got %d" % (MAX_HAND_SCALES, len(scales)))
+        for s in scales:
+            if not (np.isfinite(s) and s > 0 and int(np.rint(s * HAND_BOXSIZE)) >= MIN_HAND_SCALE_PX):
+                raise ValueError("hand scale %r: expected a finite number > 0 with round(s * %d) >= %d"
+                                 % (s, HAND_BOXSIZE, MIN_HAND_SCALE_PX))
+    if not isinstance(flip_left, (bool, np.bool_)):
+        raise ValueError("flip_left must be a bool, got %r" % (flip_left,))
+    return {"hand_scales": scales, "flip_left": bool(flip_left)}
+
+
+def flip_array(flip, n):
+    """A per-crop mirror flag sequence as the uint8 host array the *_flip / *_ex entry points
+    take, or None (NULL) when no crop is mirrored.  ValueError if its length is not n."""
+    if flip is None:
+        return None
+    f = [bool(v) for v in flip]
+    if len(f) != n:
+        raise ValueError("flip needs one flag per crop: %d flags for %d crops" % (len(f), n))
+    return (ctypes.c_uint8 * n)(*[int(v) for v in f]) if any(f) else None
+
+
 LIB_PATH = os.environ.get("ISLPOSE_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "libislpose.so"))
 
 # every symbol include/islpose.h declares
@@ -82,7 +124,8 @@ EXPORTS = ["isl_abi_version", "isl_last_error", "isl_net_create", "isl_net_destr
            "isl_net_op_info", "isl_net_set_graph", "isl_lane_stream_create", "isl_lane_stream_destroy",
            "isl_net_set_precision", "isl_net_get_precision", "isl_net_set_act_storage",
            "isl_net_get_act_storage", "isl_net_act_storage_active", "isl_post_opts_default",
-           "isl_body_post_opts", "isl_hand_post_opts", "isl_hand_post_crops_opts"]
+           "isl_body_post_opts", "isl_hand_post_opts", "isl_hand_post_crops_opts",
+           "isl_net_preprocess_crops_flip", "isl_hand_post_ex", "isl_hand_post_crops_ex"]
 
 
 class IslCaps(ctypes.Structure):
@@ -177,6 +220,11 @@ def lib():
     L.isl_body_post_opts.argtypes = L.isl_body_post.argtypes + [po]
     L.isl_hand_post_opts.argtypes = L.isl_hand_post.argtypes + [po]
     L.isl_hand_post_crops_opts.argtypes = L.isl_hand_post_crops.argtypes + [po]
+    pu8 = ctypes.POINTER(ctypes.c_uint8)
+    L.isl_net_preprocess_crops_flip.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(IslCrop), pu8, i32, dbl,
+                                                ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
+    L.isl_hand_post_ex.argtypes = L.isl_hand_post_opts.argtypes + [pu8, vp]
+    L.isl_hand_post_crops_ex.argtypes = L.isl_hand_post_crops_opts.argtypes + [pu8, vp]
     for name in EXPORTS[2:]:
         getattr(L, name).restype = i32
     if L.isl_abi_version() != 1:
@@ -530,12 +578,20 @@ class Net:
                                        ctypes.byref(nw), stream_handle(stream)), "isl_net_preprocess")
         return nh.value, nw.value
 
-    def preprocess_crops(self, frames_u8, crops, scale_times_box: float, stream=None):
+    def preprocess_crops(self, frames_u8, crops, scale_times_box: float, stream=None, flip=None):
         """frames uint8 [n,H,W,3] cuda; crops [(frame, x, y, w, h)] -> fills one net-input
-        slot per crop (Hand.__call__'s resize of each crop); returns (net_h, net_w)."""
+        slot per crop (Hand.__call__'s resize of each crop); returns (net_h, net_w).
+        flip: one bool per crop, None for none -- a flagged crop's slot is that of the
+        contiguous crop[:, ::-1] (isl_net_preprocess_crops_flip)."""
         n, H, W, _ = frames_u8.shape
         arr = (IslCrop * len(crops))(*[IslCrop(*map(int, c)) for c in crops])
         nh, nw = ctypes.c_int32(), ctypes.c_int32()
+        fl = flip_array(flip, len(crops))
+        if fl is not None:
+            check(lib().isl_net_preprocess_crops_flip(self.h, ptr(frames_u8), n, H, W, arr, fl, len(crops),
+                                                      float(scale_times_box), ctypes.byref(nh), ctypes.byref(nw),
+                                                      stream_handle(stream)), "isl_net_preprocess_crops_flip")
+            return nh.value, nw.value
         check(lib().isl_net_preprocess_crops(self.h, ptr(frames_u8), n, H, W, arr, len(crops), float(scale_times_box),
                                              ctypes.byref(nh), ctypes.byref(nw), stream_handle(stream)),
               "isl_net_preprocess_crops")

@@ -14,6 +14,17 @@ post-processing options of ``Body`` and ``Hand`` (islpose.runtime.check_post_opt
 estimators this object builds; ``max_people=1`` keeps the best-scoring person, so at most two
 hand crops per frame reach the hand nets.  None is the reference's constant (no cap).
 
+``hand_scales``, ``flip_left``, ``hand_info`` (keyword only, not in the reference): the hand-path
+options (islpose.runtime.check_hand_opts).  ``hand_scales`` is the hand pyramid (None: the
+reference's (0.5, 1.0, 1.5, 2.0); OpenPose's own default is one scale).  ``flip_left`` mirrors
+every crop handDetect marks ``is_left`` before the one-handedness hand net and mirrors its
+keypoints back, as OpenPose's extractor does (the reference inherited pytorch-openpose's
+omission of that step).  ``hand_info`` makes every result a 4-tuple whose fourth item is a list
+aligned with ``all_hand_peaks`` of ``dict(person=subset row, is_left=bool, box=(x, y, w),
+scores=float64[21])`` -- the score is the scale-averaged map at the keypoint, 0.0 for a part that
+was not found; without it the result is the reference's 3-tuple.  ``hands_for(frames, body_results)``
+is everything after the body (boxes -> hand peaks -> assembled results) for given body results.
+
 ``ISLSignPosTranslator(body_model, hand_model, translation_model)`` (:308-443)
 turns a 20-frame window into [1, 20, 156] ``populate_features`` rows and applies
 ``translation_model`` -- a keras-free ``islpose.translate.SignClassifier`` (one
@@ -53,8 +64,13 @@ def _as_numpy(img):
 
 
 class ISLSignPos(object):
-    def __init__(self, pt_body_model, pt_hand_model, *, thre1=None, thre2=None, hand_thre=None, max_people=None):
+    def __init__(self, pt_body_model, pt_hand_model, *, thre1=None, thre2=None, hand_thre=None, max_people=None,
+                 hand_scales=None, flip_left=False, hand_info=False):
         self.post_opts = rt.check_post_opts(thre1=thre1, thre2=thre2, hand_thre=hand_thre, max_people=max_people)
+        self.hand_opts = rt.check_hand_opts(hand_scales=hand_scales, flip_left=flip_left)
+        if not isinstance(hand_info, (bool, np.bool_)):
+            raise ValueError("hand_info must be a bool, got %r" % (hand_info,))
+        self.hand_info = bool(hand_info)
         self.pt_body = pt_body_model
         self.pt_hand = pt_hand_model
         self.njoint_body = 26
@@ -82,7 +98,8 @@ class ISLSignPos(object):
                                        max_people=self.post_opts["max_people"])
             bnet.set_graph(GRAPH_REPLAY[0])
         if self._hand is None or self._hand.net is not hnet:
-            self._hand = HandEstimator(device=dev, net=hnet, thre=self.post_opts["hand_thre"])
+            self._hand = HandEstimator(device=dev, net=hnet, thre=self.post_opts["hand_thre"],
+                                       scale_search=self.hand_opts["hand_scales"])
             hnet.set_graph(GRAPH_REPLAY[1])
         return self._body, self._hand
 
@@ -90,14 +107,16 @@ class ISLSignPos(object):
         """Identity of what produces the keypoints: the two modules, their current
         parameters (storage and in-place version, as _NativeNet.native() tracks them)
         and the native nets' split-K state and precision (src.model set_precision), and the
-        post-processing options (thre1, thre2, hand_thre, max_people)."""
+        post-processing options (thre1, thre2, hand_thre, max_people) and the hand-path options
+        (hand_scales, flip_left, hand_info)."""
         def part(m):
             if m is None:
                 return (None,)
             net = getattr(m, "_native_net", None)
             return (id(m), tuple((p.data_ptr(), p._version) for p in m.parameters()),
                     getattr(net, "split_k", None), getattr(m, "precision", None))
-        return part(self.pt_body) + part(self.pt_hand) + tuple(sorted(self.post_opts.items()))
+        return (part(self.pt_body) + part(self.pt_hand) + tuple(sorted(self.post_opts.items())) +
+                tuple(sorted(self.hand_opts.items())) + (("hand_info", self.hand_info),))
 
     def bodypos(self, oriImg):
         return self._estimators()[0].estimate(np.ascontiguousarray(_as_numpy(oriImg), dtype=np.uint8))
@@ -157,14 +176,49 @@ class ISLSignPos(object):
             t = frames.contiguous()
         else:
             t = torch.from_numpy(np.ascontiguousarray(_as_numpy(frames), dtype=np.uint8)).to("cuda:%d" % body.device)
-        res = body.estimate(t)
-        boxes = []
-        for i, (c, s) in enumerate(res):
+        return self.hands_for(t, body.estimate(t), (body, hand))
+
+    def hands_for(self, frames_t, body_results, ests=None, defer=False):
+        """Everything after the body: frames_t cuda uint8 [n, H, W, 3], body_results
+        [(candidate, subset)] * n -> the results of call_batch: util.hand_boxes per frame (in
+        the reference's order), every hand crop of the batch as one batch per scale
+        (HandEstimator.estimate_crops), the peaks offset into frame coordinates (_assemble).
+        With flip_left the crops whose is_left is true run mirrored and their keypoints come
+        back in the crop's own coordinates before _assemble, which is unchanged -- including the
+        reference's quirk that a coordinate equal to 0 is not offset (ISL_Model_parameter.py:
+        56-59), so a part that was not found and one found in the crop's first column or row
+        look alike there; hand_info's scores (0.0: not found) tell them apart.
+        defer: enqueue on the current stream without waiting (HandEstimator.launch_crops) and
+        return a callable that completes the call and returns the results."""
+        hand = (ests or self._estimators())[1]
+        boxes, meta = [], []
+        for i, (c, s) in enumerate(body_results):
             # handDetect reads only the frame's shape (util.py:245)
-            for x, y, w, _is_left in util.handDetect(c, s, t[i]):
+            for x, y, w, is_left, row in util.hand_boxes(c, s, frames_t[i]):
                 boxes.append((i, x, y, w))
-        peaks = hand.estimate_crops(t, boxes)
-        return self._assemble(res, boxes, peaks)
+                meta.append((row, bool(is_left)))
+        flip = [m[1] for m in meta] if self.hand_opts["flip_left"] else None
+        kw = {}
+        if flip is not None:
+            kw["flip"] = flip
+        if self.hand_info:
+            kw["return_scores"] = True
+        if defer:
+            job = hand.launch_crops(frames_t, boxes, **kw)
+            return lambda: self._hand_results(body_results, boxes, meta, hand.finish_crops(job))
+        return self._hand_results(body_results, boxes, meta, hand.estimate_crops(frames_t, boxes, **kw))
+
+    def _hand_results(self, res, boxes, meta, peaks):
+        scores = None
+        if isinstance(peaks, tuple):
+            peaks, scores = peaks
+        out = self._assemble(res, boxes, peaks)
+        if not self.hand_info:
+            return out
+        infos = [[] for _ in res]
+        for (i, x, y, w), (row, is_left), sc in zip(boxes, meta, scores):
+            infos[i].append(dict(person=int(row), is_left=is_left, box=(x, y, w), scores=sc.copy()))
+        return [(c, s, pk, info) for (c, s, pk), info in zip(out, infos)]
 
     @staticmethod
     def _assemble(res, boxes, peaks):
@@ -188,23 +242,22 @@ class ISLSignPos(object):
         if getattr(self, "_pipe_streams", None) is None:
             self._pipe_streams = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
         sb, sh = self._pipe_streams
-        prev = None                                  # (key, body results, boxes, hand job)
+        prev = None                                  # (key, the hands' deferred results)
         for key, t in batches:
             sb.wait_stream(cur)
             with torch.cuda.stream(sb):
                 bjob = body.launch(t)
             t.record_stream(sb)
             if prev is not None:                     # its hands ran beside this body
-                yield prev[0], self._assemble(prev[1], prev[2], hand.finish_crops(prev[3]))
+                yield prev[0], prev[1]()
             res = body.finish(bjob)
-            boxes = [(i, x, y, w) for i, (c, s) in enumerate(res) for x, y, w, _l in util.handDetect(c, s, t[i])]
             sh.wait_stream(cur)
             with torch.cuda.stream(sh):
-                hjob = hand.launch_crops(t, boxes)
+                done = self.hands_for(t, res, (body, hand), defer=True)
             t.record_stream(sh)
-            prev = (key, res, boxes, hjob)
+            prev = (key, done)
         if prev is not None:
-            yield prev[0], self._assemble(prev[1], prev[2], hand.finish_crops(prev[3]))
+            yield prev[0], prev[1]()
 
 
 class ISLSignPosTranslator(ISLSignPos):
@@ -213,9 +266,9 @@ class ISLSignPosTranslator(ISLSignPos):
     cache_frames = 64   # per-frame feature rows kept for overlapping windows
 
     def __init__(self, body_model, hand_model, translation_model, *, thre1=None, thre2=None, hand_thre=None,
-                 max_people=None):
+                 max_people=None, hand_scales=None, flip_left=False, hand_info=False):
         super().__init__(body_model, hand_model, thre1=thre1, thre2=thre2, hand_thre=hand_thre,
-                         max_people=max_people)
+                         max_people=max_people, hand_scales=hand_scales, flip_left=flip_left, hand_info=hand_info)
         self.model_type = 'body25'
         self.translation_layer = translation_model
         self._rows = collections.OrderedDict()
@@ -237,7 +290,7 @@ class ISLSignPosTranslator(ISLSignPos):
         frames = _as_numpy(frames)
         rows = []
         for s in range(0, len(frames), batch):
-            rows.extend(self.frame_features(*r) for r in self.call_batch(frames[s:s + batch]))
+            rows.extend(self.frame_features(*r[:3]) for r in self.call_batch(frames[s:s + batch]))
         return np.array(rows, dtype=np.float64).reshape(len(rows), translate.N_FEATURES)
 
     def cached_features(self, frames):
@@ -257,7 +310,7 @@ class ISLSignPosTranslator(ISLSignPos):
         if miss:
             res = self.call_batch(np.stack([frames[i] for i in miss]))
             for i, r in zip(miss, res):
-                self._rows[keys[i]] = self.frame_features(*r)
+                self._rows[keys[i]] = self.frame_features(*r[:3])
         rows = []
         for k in keys:
             self._rows.move_to_end(k)

@@ -94,6 +94,23 @@ def handDetect(candidate, subset, oriImg):
     return result
 
 
+def hand_boxes(candidate, subset, oriImg):
+    """handDetect's boxes with the person they belong to (not in the reference):
+    [[x, y, w, is_left, person_row], ...] -- the first four fields and the order are
+    handDetect's, person_row is the row of `subset` whose arm produced the box."""
+    result = []
+    if len(subset) == 0:
+        return result
+    # only persons with a whole arm reach handDetect (its own has_left / has_right test, for
+    # every row at once), each as a one-row subset
+    person = np.asarray(subset).astype(int)
+    whole = (person[:, [5, 6, 7]] != -1).all(axis=1) | (person[:, [2, 3, 4]] != -1).all(axis=1)
+    for row in np.nonzero(whole)[0]:
+        for box in handDetect(candidate, subset[row:row + 1], oriImg):
+            result.append(box + [int(row)])
+    return result
+
+
 def get_bodypose(candidate, subset, model_type="coco"):
     """Export tuples: ([(x, y) per present joint], [(mY, mX, angle, length) per present limb])."""
     limbs, njoint = (BODY25_LIMBS, 25) if model_type == "body25" else (COCO_LIMBS, 18)

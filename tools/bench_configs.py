@@ -64,7 +64,8 @@ def c3(args):
     from islpose.hand import HandEstimator, HAND_SCALES
     B, H, W = args.batch, 368, 656
     body = BodyEstimator(synth.synth_weights(0), "body25", scale_search=(0.5,), max_people=args.max_people)
-    hand = HandEstimator(synth.synth_weights(2))
+    scales = args.hand_scales or HAND_SCALES
+    hand = HandEstimator(synth.synth_weights(2), scale_search=scales)
     frames = torch.from_numpy(synth.synth_frames(B, H, W, seed=5)).cuda()
     (m, nh, nw, vh, vw), = scale_geometry(H, W, (0.5,))
     maps = [synth.designed_pose_maps(nh // 8, nw // 8, 1, seed=i) for i in range(B)]
@@ -76,10 +77,11 @@ def c3(args):
         for _ in range(2):
             w = int(rng.randint(120, 201))
             boxes.append((f, int(rng.randint(0, W - w)), int(rng.randint(0, H - w)), w))
+    flip = [k % 2 == 0 for k in range(len(boxes))] if args.flip_left else None   # the first crop of a frame: left
 
     # designed hand maps for the post (random weights give dense maps: one giant component
     # per plane, unlike real footage); the hand nets still run in full on every crop
-    hgeo = [(s * 368 // 8, s * 368 // 8) for s in (0.5, 1.0, 1.5, 2.0)]
+    hgeo = [((round(s * 368) + 7) // 8, (round(s * 368) + 7) // 8) for s in scales]
     hmaps = [torch.from_numpy(np.stack([synth.designed_hand_maps(int(hh), int(ww), seed=31 * i + k)
                                         for i in range(len(boxes))])).cuda()
              for k, (hh, ww) in enumerate(hgeo)]
@@ -88,16 +90,16 @@ def c3(args):
         body.net.preprocess(frames, m)
         body.net.run()
         body.post_maps(H, W, [(nh, nw, vh, vw)], [paf], [heat], details=False)
-        heats = hand.run_crops(frames, boxes)
-        hand.post_crops(boxes, hmaps if args.designed_hands else heats)
+        heats = hand.run_crops(frames, boxes, flip)
+        hand.post_crops(boxes, hmaps if args.designed_hands else heats, flip)
 
     sec = timed(step, args.steps, args.warmup)
-    gf = B * conv_gflop(0, nh, nw) + len(boxes) * sum(conv_gflop(2, s, s) for s in (184, 368, 552, 736))
+    gf = B * conv_gflop(0, nh, nw) + len(boxes) * sum(conv_gflop(2, 8 * hh, 8 * ww) for hh, ww in hgeo)
     return {"config": "C3 body_25 + hand (2 crops/frame, 4 scales)", "batch": B, "crops": len(boxes),
             "hand_crops_per_frame": round(len(boxes) / B, 2), "max_people": args.max_people,
             "frames_per_s": round(B / sec, 2), "ms_per_step": round(sec * 1e3, 2),
             "conv_gflop_per_step": round(gf, 1), "conv_tflops_fp32_equiv_wall": round(gf / sec / 1e3, 1),
-            "hand_scales": list(HAND_SCALES),
+            "hand_scales": list(scales), "flip_left": bool(args.flip_left),
             "hand_post_on": "designed maps" if args.designed_hands else "raw net output (random weights: dense maps)"}
 
 
@@ -151,11 +153,12 @@ def c5(args):
     del cal
     tw = lambda d: {k: torch.from_numpy(v) for k, v in d.items()}  # noqa: E731
     isl = ISLSignPos(Body(tw(wb), "body25").model, Hand(tw(synth.synth_weights(2))).model,
-                     max_people=args.max_people)
+                     max_people=args.max_people, hand_scales=args.hand_scales, flip_left=args.flip_left)
     clips = {"v%d.mp4" % k: rgb for k in range(args.c5_videos)}
     rows = [{"Filepath": f, "type": "Greetings", "expression": "hello"} for f in clips]
     res = {"config": "C5 video -> per-frame JSON, 1080x1920 RGB frames", "frames": T * len(rows),
            "videos": len(rows), "batch": B, "export": False, "max_people": args.max_people,
+           "hand_scales": list(isl.hand_opts["hand_scales"]), "flip_left": bool(args.flip_left),
            "decode": "frames already decoded in host memory (pims/ffmpeg absent); the pipeline reads them as "
                      "slices of the [T,H,W,3] array"}
     for ov in ((True,) if args.c5_overlap_only else (False, True)):
@@ -200,7 +203,7 @@ def frame(args):
     del cal
     tw = lambda d: {k: torch.from_numpy(v) for k, v in d.items()}  # noqa: E731
     isl = ISLSignPos(Body(tw(wb), "body25").model, Hand(tw(synth.synth_weights(2))).model,
-                     max_people=args.max_people)
+                     max_people=args.max_people, hand_scales=args.hand_scales, flip_left=args.flip_left)
     body = isl._estimators()[0]
     for i in range(min(5, T)):          # warm-up: arenas of the body and of the hand crop sizes
         isl.call(rgb[i][:, :, ::-1])
@@ -251,10 +254,52 @@ def frame(args):
             "body_ms_per_frame": round(db / T * 1e3, 3), "hand_ms_per_frame": round((dt - db) / T * 1e3, 3),
             "hand_crops_per_frame": round(crops / T, 2), "persons_per_frame": round(persons / R / T, 2),
             "max_people": args.max_people,
+            "hand_scales": list(isl.hand_opts["hand_scales"]), "flip_left": bool(args.flip_left),
             "crop_width_px": [int(min(widths)), int(max(widths))] if widths else [],
             "basis": "wall time of T sequential calls (host frame -> pinned H2D -> GPU flip -> body net + post -> "
                      "handDetect -> hand crops batched per scale -> peaks on the host); body = upload + estimate + "
                      "handDetect on the same frames, hand = the rest"}
+
+
+def hands2(args):
+    """ISLSignPos.hands_for per 1080x1920 frame on a designed one-person body result whose two
+    arms give one left and one right hand box of about 300 px: the signer workload's hand path
+    alone (boxes -> hand nets per scale -> posts -> assembled results on the host)."""
+    from islpose import synth
+    from src import util
+    from src.body import Body
+    from src.hand import Hand
+    from src.ISL_Model_parameter import ISLSignPos
+    T, H, W = args.frame_count, 1080, 1920
+    tw = lambda d: {k: torch.from_numpy(v) for k, v in d.items()}  # noqa: E731
+    isl = ISLSignPos(Body(tw(synth.synth_weights(0)), "body25").model, Hand(tw(synth.synth_weights(2))).model,
+                     hand_scales=args.hand_scales, flip_left=args.flip_left)
+    ests = isl._estimators()
+    # shoulder, elbow, wrist of the right (joints 2-4) and left (5-7) arm: forearms of 200 px
+    # -> boxes of 1.5 * 200 = 300 px
+    pts = {2: (800, 300), 3: (700, 500), 4: (700, 700), 5: (1100, 300), 6: (1200, 500), 7: (1200, 700)}
+    cand = np.array([[x, y, 0.9, k] for k, (x, y) in enumerate(pts.values())], np.float64)
+    sub = -np.ones((1, 27))
+    for k, j in enumerate(pts):
+        sub[0, j] = k
+    sub[0, -2], sub[0, -1] = 6 * 0.9, 6
+    frames = [torch.from_numpy(f[None]).cuda() for f in synth.synth_frames(T, H, W, seed=57)]
+    boxes = util.hand_boxes(cand, sub, frames[0][0])
+    crops = 0
+    for t in frames[:min(3, T)]:
+        isl.hands_for(t, [(cand, sub)], ests)
+    torch.cuda.synchronize()
+    R = max(1, args.frame_repeat)
+    t0 = time.perf_counter()
+    for _ in range(R):
+        for t in frames:
+            crops += len(isl.hands_for(t, [(cand, sub)], ests)[0][2])
+    dt = (time.perf_counter() - t0) / R
+    return {"config": "HANDS2 ISLSignPos.hands_for per 1080x1920 frame, one designed person, two hand boxes",
+            "frames": T, "passes": R, "frames_per_s": round(T / dt, 2), "ms_per_frame": round(dt / T * 1e3, 3),
+            "hand_crops_per_frame": round(crops / R / T, 2),
+            "boxes": [[int(b[0]), int(b[1]), int(b[2]), bool(b[3])] for b in boxes],
+            "hand_scales": list(isl.hand_opts["hand_scales"]), "flip_left": bool(args.flip_left)}
 
 
 def c6(args):
@@ -294,7 +339,7 @@ def c6(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", choices=["c3", "c4", "c5", "c6", "frame", "all"], default="all")
+    ap.add_argument("--config", choices=["c3", "c4", "c5", "c6", "frame", "hands2", "all"], default="all")
     ap.add_argument("--frame-count", type=int, default=64, help="FRAME: sequential per-frame calls timed")
     ap.add_argument("--frame-repeat", type=int, default=4, help="FRAME: timed passes over the frames")
     ap.add_argument("--batch", type=int, default=16, help="C3 / C4 frames per step")
@@ -317,12 +362,20 @@ def main():
     ap.add_argument("--max-people", type=int, default=None,
                     help="FRAME / C3 / C5: keep the N best-scoring persons of a frame (ISLSignPos / BodyEstimator "
                          "max_people; 1: the signer only, at most two hand crops per frame); default: no cap")
+    ap.add_argument("--hand-scales", default=None,
+                    help="FRAME / C3 / C5 / HANDS2: the hand pyramid as comma-separated scales of 368 px "
+                         "(default 0.5,1.0,1.5,2.0)")
+    ap.add_argument("--flip-left", action="store_true",
+                    help="FRAME / C3 / C5 / HANDS2: mirror left-hand crops before the hand net (C3: every first "
+                         "crop of a frame)")
     a = ap.parse_args()
+    a.hand_scales = tuple(float(v) for v in a.hand_scales.split(",")) if a.hand_scales else None
     if a.precision:
         os.environ["ISLPOSE_PRECISION"] = a.precision   # read by every net at its creation
     if a.act_storage:
         os.environ["ISLPOSE_ACT_STORAGE"] = a.act_storage
-    for name, fn in (("c3", c3), ("c4", c4), ("c5", c5), ("c6", c6), ("frame", frame)):
+    for name, fn in (("c3", c3), ("c4", c4), ("c5", c5), ("c6", c6), ("frame", frame),
+                     ("hands2", hands2)):
         if a.config in (name, "all"):
             res = fn(a)
             res["precision"] = os.environ.get("ISLPOSE_PRECISION", "fp32")

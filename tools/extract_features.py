@@ -48,7 +48,17 @@ def main():
     ap.add_argument("--max-people", type=int, default=None,
                     help="keep the N best-scoring persons of a frame (1: the signer only, at most two hand "
                          "crops per frame); default: no cap")
+    ap.add_argument("--hand-scales", default=None,
+                    help="the hand pyramid as comma-separated scales of 368 px, e.g. 0.5,1.0 (hand.py:25; default "
+                         "0.5,1.0,1.5,2.0; fewer or smaller scales are faster)")
+    ap.add_argument("--flip-left", action="store_true",
+                    help="mirror left-hand crops before the hand net and the keypoints back (OpenPose's extractor; "
+                         "not in the reference)")
+    ap.add_argument("--hand-info", action="store_true",
+                    help="add a hand_info key to every frame's JSON: per hand its person, is_left, box and the 21 "
+                         "keypoint scores (0.0: not found)")
     a = ap.parse_args()
+    hand_scales = tuple(float(v) for v in a.hand_scales.split(",")) if a.hand_scales else None
 
     import torch
     from islpose import pipeline, synth
@@ -74,7 +84,8 @@ def main():
     body = Body(weights(a.body_weights, 0), "body25", precision=a.precision)
     hand = Hand(weights(a.hand_weights, 2), precision=a.precision)
     model = ISLSignPos(body.model, hand.model, thre1=a.thre1, thre2=a.thre2, hand_thre=a.hand_thre,
-                       max_people=a.max_people)
+                       max_people=a.max_people, hand_scales=hand_scales, flip_left=a.flip_left,
+                       hand_info=a.hand_info)
 
     if a.synthetic:
         T, H, W = (int(v) for v in a.synthetic.split(","))
