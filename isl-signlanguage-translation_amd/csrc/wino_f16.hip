@@ -18,29 +18,41 @@
 // the other way round, so that no operand of the K loop is shared through LDS except the raw
 // input:
 //
-//   * Block = 16 waves, wave w owns xi = w (one GEMM) for 64 output channels x 64 tiles
-//     (2 x 2 accumulator tiles of 32 x 32, 64 registers).  U[xi] of the block is used by
-//     that wave alone, so its A fragments go straight from L2 into registers (4 x 16 B per
-//     lane and K step, loaded one step ahead) -- no LDS, no barrier for the filters.
-//   * V[xi] is also used by that wave alone: the wave builds its B fragments itself from
-//     the staged fp32 input, 4 pixels per (tile, channel) -- V[r][c] = (d[ra][ca] +
-//     sc d[ra][cb]) + sr (d[rb][ca] + sc d[rb][cb]), B^T's rows having two nonzeros each --
-//     3 fma + the split per value, 24 VALU per 8 values of a fragment.
-//   * The raw input of a K step (a chunk pair) arrives by LDS-DMA, double-buffered, one
-//     barrier per step.  The block's 64 tiles are consecutive in "band order" (a band = two
-//     tile rows, walked column-pair by column-pair), so they touch at most two bands and the
-//     staged run is 6 rows x (64 + 4) columns whatever the image width (26 KB per step).
+//   * Block = 8 waves (512 threads, one block per CU, two waves per SIMD) for 64 output channels
+//     x 64 tiles x all 16 GEMMs.  Wave w owns the two GEMMs xi0 = 4 r + 2 cp, xi1 = xi0 + 1
+//     (r = w >> 1 a row of V, cp = w & 1 a column pair): 2 x 2 x 2 accumulator tiles of 32 x 32,
+//     128 registers.  U[xi0], U[xi1] of the block are used by that wave alone, so its A fragments
+//     go straight from L2 into registers (8 x 16 B per lane and K step, loaded one step ahead
+//     into the other of two register sets by counted inline-asm loads) -- no LDS, no barrier for
+//     the filters.
+//   * V[xi0], V[xi1] are also used by that wave alone: the wave builds its B fragments itself
+//     from the staged fp32 input.  B^T's rows have two nonzeros each, so a row of V is the
+//     combination t[col] = d[ra][col] + sr d[rb][col] (sr = +-1), shared by the pair over three
+//     column slots: V(xi0) = tX - tY, V(xi1) = tY + sz tZ -- 6 pixels, 3 + 2 packed fma per
+//     4 channels for the two values, then the split (v_cvt_pk_f16_f32 + v_fma_mix, 1.5 VALU per
+//     value).  sr and sz are wave-uniform and sit in scalar register pairs.
+//   * The raw input of a K step (a chunk pair) arrives by LDS-DMA into a ring of three slots, two
+//     steps ahead, one barrier per step.  The block's 64 tiles are consecutive in "band order" (a
+//     band = two tile rows, walked column-pair by column-pair), so they touch at most two bands
+//     and the staged run is 6 rows x (64 + 4) columns whatever the image width (26 KB per step).
 //     Layout [chunk half h][channel quad q][row 6][column parity][34] x 16 B: the lanes of
-//     a wave (consecutive band slots) read conflict-free ds_read_b128s (lane pairs 2k, 2k+1
-//     differ by two rows = 32 banks, lane pairs by 16 B).
-//   * Epilogue: the 16 waves' M tiles meet in LDS (two rounds of 32 channels, 128 KB), one
+//     a wave (consecutive band slots) read ds_read_b128s (lane pairs 2k, 2k+1 differ by two
+//     rows = 32 banks, lane pairs by 16 B).
+//   * A K step is four groups (tile half j, channel quad Q) of six ds_read_b128, 22 VALU and,
+//     behind each Q = 1 group, the 12 MFMAs of j.  The reads run one group ahead of their use:
+//     the first group's at the top of the step, in front of the filter loads and the DMA; the
+//     next group's as soon as the current group's row combinations are formed and its 24 raw
+//     registers are free.  Reads and their waits are inline asm, tied by operands to the work
+//     they stand behind, so the wait of a group finds its pixels landed behind the previous
+//     group's splits and MFMAs instead of straight behind the reads (what hipcc places).
+//   * Epilogue: the waves' M tiles meet in LDS (two rounds of 32 channels, 128 KB), one
 //     thread per (4 channels, tile) sums them in a fixed order into the 2x2 outputs.
 //
-// Per K step and CU (16 waves of 12 MFMAs): 1536 MFMA cycles against ~1000 LDS cycles
-// (16 ds_read_b128 per wave), ~770 VALU cycles per SIMD and 64 KB of filters + 26 KB of
-// input from L2.  Eligible launches (wino_f16_fits): 3x3, cout % 64 == 0, no fused pool or
-// pooled-input staging, at least 32 tiles per row and > 1024 pixels per frame (no
-// canonical K ranges: those layers keep conv_x3's batch-invariant sums).
+// Per K step and CU (8 waves of 24 MFMAs): 1536 MFMA cycles per SIMD, 192 KB of LDS reads
+// (24 ds_read_b128 per wave), ~130 VALU per wave and 64 KB of filters + 26 KB of input from
+// L2.  255 VGPRs, no spills, two waves per SIMD.  Eligible launches (wino_f16_fits): 3x3,
+// cout % 64 == 0, no fused pool or pooled-input staging, at least 32 tiles per row and > 1024
+// pixels per frame (no canonical K ranges: those layers keep conv_x3's batch-invariant sums).
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -87,11 +99,29 @@ __device__ __forceinline__ void split_dw(const f32x4& v, unsigned& h01, unsigned
   asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l23) : "v"(h23), "v"(v.w));
 }
 
+// the six raw pixels (4 channels each) of one (tile half, channel quad): rows ra / rb x column slots X, Y, Z
+struct W2Raw {
+  f32x4 aX, aY, aZ, bX, bY, bZ;
+};
+// s * b + a with the +-1 multiplier s in a scalar register pair: the v_pk_fma_f32 of the vector form
+__device__ __forceinline__ f32x2 pk_fma_s(unsigned long long s, f32x2 b, f32x2 a) {
+  f32x2 d;
+  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "s"(s), "v"(b), "v"(a));
+  return d;
+}
+__device__ __forceinline__ f32x2 lo2(const f32x4& v) { return f32x2{v.x, v.y}; }
+__device__ __forceinline__ f32x2 hi2(const f32x4& v) { return f32x2{v.z, v.w}; }
+
 // ABL (development build only, tools/convbench "w2" with ISLPOSE_W2_ABL): timing ablations --
 // 1 no MFMAs, 2 no transform (no raw LDS reads, no VALU; constant B), 4 no filter loads, 8 no
 // raw-input DMA, 16 no epilogue (the accumulators are folded into one store so that nothing
-// upstream is dead code).  Wrong results; libislpose.so has ABL = 0 only.
-template <int ABL>
+// upstream is dead code), 32 (on the PF = 1 loop) no raw LDS reads (the transform's VALU and the
+// MFMAs stay; the pixels come from registers the compiler cannot fold -- what the reads' round
+// trips cost); 64 + k (k = 1, 4, 8, 12, 16) ablation k on the PF = 1 loop.  Wrong results;
+// libislpose.so has ABL = 0 only.
+// PF: 1 = the raw pixels of a channel quad are read one quad ahead (below), 0 = read where they are
+// used (the development build's reference for interleaved A/B runs).
+template <int ABL, int PF>
 __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
   // [0, 3 BUF): the raw-input ring; [0, 8192): the M exchange of the epilogue; then the epilogue's
   // bias and PReLU slopes (64 + 64 floats)
@@ -138,7 +168,8 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
   // parity, half column) -> the padded input pixel; rows / columns past the buffer, which only
   // feed discarded outputs, are clamped.  The chunk is wave-uniform: a uniform base plus a
   // 32-bit lane offset.
-  int doff[4], dch[4];
+  unsigned doff[4];
+  int dch[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int p = w + 8 * e;
@@ -157,7 +188,7 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
     const int band = s1 ? bb : ba, txlo = s1 ? 0 : txlo0;
     const int rp = min(4 * band - 1 + row + a.in_pad, Hp - 1);
     const int cp = min(2 * txlo - 1 + vl + a.in_pad, Wp - 1);
-    doff[e] = ok ? (rp * Wp + cp) * 8 + qq * 4 : 0;
+    doff[e] = ok ? (unsigned)((rp * Wp + cp) * 8 + qq * 4) * 4u : 0u;   // bytes (< 2^32: wino_f16_fits)
     dch[e] = __builtin_amdgcn_readfirstlane(hp);
   }
 
@@ -171,6 +202,11 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
   const int ra = wr == 0 ? 0 : wr == 2 ? 2 : 1, rb = wr == 3 ? 3 : wr == 2 ? 1 : 2;
   const float sr = wr == 1 ? 1.f : -1.f, sz = cpr ? -1.f : 1.f;
   const f32x4 srv = f32x4{sr, sr, sr, sr}, szv = f32x4{sz, sz, sz, sz};
+  // PF: the +-1 multipliers as scalar register pairs (wave-uniform), operands of v_pk_fma_f32
+  const unsigned sru = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, sr));
+  const unsigned szu = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, sz));
+  const unsigned long long sr2 = (unsigned long long)sru << 32 | sru, sz2 = (unsigned long long)szu << 32 | szu;
+  const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) void*)smem;
   const int cX = cpr ? 2 : 0, cY = cpr ? 1 : 2, cZ = cpr ? 3 : 1;
   auto toff = [&](int row, int col) { return (row * 2 + (col & 1)) * RS + (col >> 1); };
   const int to_aX = toff(ra, cX), to_aY = toff(ra, cY), to_aZ = toff(ra, cZ);
@@ -215,7 +251,9 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
     for (int e = 0; e < 4; ++e) {
       const int ch = min(2 * k + dch[e], a.cin_chunks - 1);   // a missing odd chunk: zero filters
       const float* src = in_f + (size_t)ch * a.in_chs;
-      __builtin_amdgcn_global_load_lds((const void*)(src + doff[e]),
+      unsigned d = doff[e];
+      asm volatile("" : "+v"(d));   // widened per use: four registers across the loop, not eight
+      __builtin_amdgcn_global_load_lds((const void*)((const char*)src + (size_t)d),
                                        (__attribute__((address_space(3))) void*)(smem + sl * BUF + (w + 8 * e) * 64),
                                        16, 0, 0);
     }
@@ -234,7 +272,115 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
   // inf or NaN (a zero filter gives NaN too), so the epilogue's output check raises the range flag
   // (the host then recomputes on the fp32 kernels); |V| in [65504, 65520) splits exactly.
 
-  // per tile tile j: both GEMMs' B fragments (the transform) from ring slot sl, then 12 MFMAs
+  // PF = 1: the K step's four (tile half j, channel quad Q) groups in the order (0, 0), (0, 1),
+  // (1, 0), (1, 1), the same V values, splits and MFMAs as below in the same order.  The six
+  // ds_read_b128 of a group are issued one group ahead: those of (0, 0) at the top of the step,
+  // in front of the step's filter loads and DMA; those of group g + 1 as soon as the row
+  // combinations t of group g are formed and its raw registers are dead, so that they land behind
+  // group g's differences and splits and, after a Q = 1 group, behind the 12 MFMAs of j.  Reads
+  // and waits are inline asm (the compiler would put s_waitcnt lgkmcnt(0) straight behind each
+  // read); one group is outstanding at a wait, so its count is 0.  Every read of a step has landed
+  // before the step's barrier: the ring's hazards are those of PF = 0.
+  const unsigned oaX = lds0 + 16 * to_aX, oaY = lds0 + 16 * to_aY, oaZ = lds0 + 16 * to_aZ;
+  const unsigned obX = lds0 + 16 * to_bX, obY = lds0 + 16 * to_bY, obZ = lds0 + 16 * to_bZ;
+  // t: the issuing group's six row combinations, input operands of the reads' asm (which does not
+  // use them), so that the reads stand behind them (null at the step's top)
+  auto rd = [&](W2Raw& r, int sl, int j, auto qc, f32x2* t) __attribute__((always_inline)) {
+    constexpr int OFF = decltype(qc)::value * QS * 16;
+    if constexpr ((ABL & 32) != 0) {
+      // whatever the 24 registers hold (earlier pixels and fragments): no read, nothing to fold
+      asm volatile("" : "=v"(r.aX), "=v"(r.bX), "=v"(r.aY), "=v"(r.bY), "=v"(r.aZ), "=v"(r.bZ));
+      return;
+    }
+    unsigned b = (unsigned)(tb[j] + sl * BUF) * 16;
+    asm volatile("" : "+v"(b));   // the pixel addresses are formed per group (not held across it)
+    const unsigned paX = b + oaX, paY = b + oaY, paZ = b + oaZ, pbX = b + obX, pbY = b + obY, pbZ = b + obZ;
+#define W2_READS                           \
+  "ds_read_b128 %0, %6 offset:%12\n\t"     \
+  "ds_read_b128 %1, %7 offset:%12\n\t"     \
+  "ds_read_b128 %2, %8 offset:%12\n\t"     \
+  "ds_read_b128 %3, %9 offset:%12\n\t"     \
+  "ds_read_b128 %4, %10 offset:%12\n\t"    \
+  "ds_read_b128 %5, %11 offset:%12"
+    if (t)
+      asm volatile(W2_READS
+                   : "=&v"(r.aX), "=&v"(r.bX), "=&v"(r.aY), "=&v"(r.bY), "=&v"(r.aZ), "=&v"(r.bZ)
+                   : "v"(paX), "v"(pbX), "v"(paY), "v"(pbY), "v"(paZ), "v"(pbZ), "n"(OFF), "v"(t[0]), "v"(t[1]),
+                     "v"(t[2]), "v"(t[3]), "v"(t[4]), "v"(t[5])
+                   : "memory");
+    else
+      asm volatile(W2_READS
+                   : "=&v"(r.aX), "=&v"(r.bX), "=&v"(r.aY), "=&v"(r.bY), "=&v"(r.aZ), "=&v"(r.bZ)
+                   : "v"(paX), "v"(pbX), "v"(paY), "v"(pbY), "v"(paZ), "v"(pbZ), "n"(OFF)
+                   : "memory");
+#undef W2_READS
+  };
+  auto compute_pf = [&](const f16x8 (&A)[2][2][2], int sl, W2Raw r) __attribute__((always_inline)) {
+    unsigned Bd[2][2][4];   // [xi][hi|lo] x 4 dwords, quad Q in dwords 2Q, 2Q + 1
+    auto group = [&](auto jc, auto qc) __attribute__((always_inline)) {
+      constexpr int j = decltype(jc)::value, Q = decltype(qc)::value;
+      // The wait for this group's pixels.  Its in-out operands keep it behind the work the reads
+      // are meant to land behind (the asm does not touch them): after a Q = 0 group that group's
+      // eight fragment dwords, after a Q = 1 group the first two accumulators of its MFMAs (six of
+      // the twelve; the other six may run beside this group's VALU).
+      if constexpr ((ABL & 32) != 0) {
+      } else if constexpr (j == 0 && Q == 0) {
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(r.aX), "+v"(r.bX), "+v"(r.aY), "+v"(r.bY), "+v"(r.aZ), "+v"(r.bZ)
+                     :
+                     : "memory");
+      } else if constexpr (Q == 1) {
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(r.aX), "+v"(r.bX), "+v"(r.aY), "+v"(r.bY), "+v"(r.aZ), "+v"(r.bZ), "+v"(Bd[0][0][0]),
+                       "+v"(Bd[0][0][1]), "+v"(Bd[0][1][0]), "+v"(Bd[0][1][1]), "+v"(Bd[1][0][0]), "+v"(Bd[1][0][1]),
+                       "+v"(Bd[1][1][0]), "+v"(Bd[1][1][1])
+                     :
+                     : "memory");
+      } else {
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(r.aX), "+v"(r.bX), "+v"(r.aY), "+v"(r.bY), "+v"(r.aZ), "+v"(r.bZ), "+v"(acc[0][0][0]),
+                       "+v"(acc[0][1][0])
+                     :
+                     : "memory");
+      }
+      f32x2 t[6];
+      t[0] = pk_fma_s(sr2, lo2(r.bX), lo2(r.aX)), t[1] = pk_fma_s(sr2, hi2(r.bX), hi2(r.aX));
+      t[2] = pk_fma_s(sr2, lo2(r.bY), lo2(r.aY)), t[3] = pk_fma_s(sr2, hi2(r.bY), hi2(r.aY));
+      t[4] = pk_fma_s(sr2, lo2(r.bZ), lo2(r.aZ)), t[5] = pk_fma_s(sr2, hi2(r.bZ), hi2(r.aZ));
+      // the next group's reads, into the raw registers that died just above
+      if constexpr (Q == 0) rd(r, sl, j, std::integral_constant<int, 1>{}, t);
+      else if constexpr (j == 0) rd(r, sl, 1, std::integral_constant<int, 0>{}, t);
+      // nothing of the group's remaining work (nor its MFMAs) is scheduled in front of the reads
+      if constexpr (j == 0 || Q == 0) __builtin_amdgcn_sched_barrier(0);
+      const f32x2 v00 = t[0] - t[2], v01 = t[1] - t[3];
+      const f32x2 v10 = pk_fma_s(sz2, t[4], t[2]), v11 = pk_fma_s(sz2, t[5], t[3]);
+      split_dw(f32x4{v00.x, v00.y, v01.x, v01.y}, Bd[0][0][2 * Q], Bd[0][0][2 * Q + 1], Bd[0][1][2 * Q], Bd[0][1][2 * Q + 1]);
+      split_dw(f32x4{v10.x, v10.y, v11.x, v11.y}, Bd[1][0][2 * Q], Bd[1][0][2 * Q + 1], Bd[1][1][2 * Q], Bd[1][1][2 * Q + 1]);
+      if constexpr (Q == 1) {
+        f16x8 Bh[2], Bl[2];
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+          Bh[x] = __builtin_bit_cast(f16x8, u32x4{Bd[x][0][0], Bd[x][0][1], Bd[x][0][2], Bd[x][0][3]});
+          Bl[x] = __builtin_bit_cast(f16x8, u32x4{Bd[x][1][0], Bd[x][1][1], Bd[x][1][2], Bd[x][1][3]});
+        }
+#pragma unroll
+        for (int x = 0; x < 2; ++x)
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            if constexpr ((ABL & 1) != 0) continue;
+            acc[x][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[x][i][0], Bh[x], acc[x][i][j], 0, 0, 0);
+            acc[x][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[x][i][0], Bl[x], acc[x][i][j], 0, 0, 0);
+            acc[x][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[x][i][1], Bh[x], acc[x][i][j], 0, 0, 0);
+          }
+      }
+    };
+    group(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+    group(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
+    group(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
+    group(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
+  };
+
+  // PF = 0.  per tile tile j: both GEMMs' B fragments (the transform) from ring slot sl, then 12 MFMAs
   auto compute = [&](const f16x8 (&A)[2][2][2], int sl) __attribute__((always_inline)) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -298,6 +444,8 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
   __syncthreads();                                       // (and the epilogue constants are staged)
   __builtin_amdgcn_sched_barrier(0);
   auto step = [&](int k, f16x8 (&A)[2][2][2], f16x8 (&An)[2][2][2]) __attribute__((always_inline)) {
+    W2Raw r0;
+    if constexpr (PF != 0) rd(r0, k % 3, 0, std::integral_constant<int, 0>{}, nullptr);
     load_a(An, min(k + 1, a.pairs - 1));
     dma(min(k + 2, a.pairs - 1), (k + 2) % 3);
     __builtin_amdgcn_sched_barrier(0);
@@ -307,7 +455,8 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
                      "+v"(A[1][0][1]), "+v"(A[1][1][0]), "+v"(A[1][1][1])
                    :
                    : "memory");
-    compute(A, k % 3);
+    if constexpr (PF != 0) compute_pf(A, k % 3, r0);
+    else compute(A, k % 3);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -452,15 +601,26 @@ hipError_t launch_wino_f16(const ConvLaunch& c, hipStream_t s) {
   if (nb <= 0 || nb > 0x7fffffff) { set_error("wino_f16: bad grid"); return hipErrorInvalidValue; }
   a.nblocks = (int)nb;
 #ifdef ISLPOSE_DEV
+  // ablations 1 .. 31 are those of the PF = 0 loop; ISLPOSE_W2_PF=0 runs that loop whole
   const int abl = getenv("ISLPOSE_W2_ABL") ? atoi(getenv("ISLPOSE_W2_ABL")) : 0;
   switch (abl) {
-#define W2ABL(k) case k: hipLaunchKernelGGL(wino_f16<k>, dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+#define W2ABL(k) case k: hipLaunchKernelGGL((wino_f16<k, 0>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
     W2ABL(1) W2ABL(2) W2ABL(3) W2ABL(4) W2ABL(6) W2ABL(8) W2ABL(12) W2ABL(14) W2ABL(16) W2ABL(31)
 #undef W2ABL
+    case 65: hipLaunchKernelGGL((wino_f16<1, 1>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+    case 68: hipLaunchKernelGGL((wino_f16<4, 1>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+    case 72: hipLaunchKernelGGL((wino_f16<8, 1>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+    case 76: hipLaunchKernelGGL((wino_f16<12, 1>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+    case 80: hipLaunchKernelGGL((wino_f16<16, 1>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+    case 32: hipLaunchKernelGGL((wino_f16<32, 1>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
     default: break;
   }
+  if (getenv("ISLPOSE_W2_PF") && atoi(getenv("ISLPOSE_W2_PF")) == 0) {
+    hipLaunchKernelGGL((wino_f16<0, 0>), dim3(a.nblocks), dim3(512), 0, s, a);
+    return hipGetLastError();
+  }
 #endif
-  hipLaunchKernelGGL(wino_f16<0>, dim3(a.nblocks), dim3(512), 0, s, a);
+  hipLaunchKernelGGL((wino_f16<0, 1>), dim3(a.nblocks), dim3(512), 0, s, a);
   return hipGetLastError();
 }
 

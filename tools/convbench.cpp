@@ -146,7 +146,13 @@ int main(int argc, char** argv) {
         if (a == "wino" && wb && ks == 3) { c.bco = wb; c.wpk = wu; return launch_wino(c, 0); }
         if (a == "wx3" && ks == 3) { c.wx3 = wux; return launch_wino_x3(c, 0); }
         // w2: the split-fp16 Winograd kernel wino_f16 (ISLPOSE_W2_ABL: its timing ablations)
-        if (a == "w2" && ww && wino_f16_fits(c)) { c.wx3 = ww; return launch_wino_f16(c, 0); }
+        // w2o: the same kernel with the raw pixels read where they are used (ISLPOSE_W2_PF=0, the
+        // loop before the one-group-ahead reads), for interleaved A/B against w2
+        if ((a == "w2" || a == "w2o") && ww && wino_f16_fits(c)) {
+          setenv("ISLPOSE_W2_PF", a == "w2o" ? "0" : "1", 1);
+          c.wx3 = ww;
+          return launch_wino_f16(c, 0);
+        }
         return hipErrorNotSupported;
       };
       if (launch() != hipSuccess) continue;
@@ -176,7 +182,7 @@ int main(int argc, char** argv) {
         CK(hipEventElapsedTime(&ms, e0, e1));
       }
       const double us = ms * 1e3 / iters;
-      const double fac = (a == "x3" || a == "x3f" || a == "x3m" || a == "x3h" || a == "x3p" || a == "x3d") ? 3.0 : (a == "wx3" || a == "w2") ? 3.0 * 16 / 36 : a == "wino" ? 16.0 / 36 : 1.0;
+      const double fac = (a == "x3" || a == "x3f" || a == "x3m" || a == "x3h" || a == "x3p" || a == "x3d") ? 3.0 : (a == "wx3" || a == "w2" || a == "w2o") ? 3.0 * 16 / 36 : a == "wino" ? 16.0 / 36 : 1.0;
       printf("  round %d %-7s %9.1f us  fp32-equiv %7.1f TF  alg-MFMA %7.1f TF\n", r, a.c_str(), us,
              flops / us / 1e6, fac * flops / us / 1e6);
     }
