@@ -411,6 +411,44 @@ int isl_sign_param_count(int n_features, int n_classes, int64_t* count);
 int isl_sign_classify(const float* d_params, int n_features, int window, int n_classes,
                       const float* d_windows, int batch, float* d_probs, void* stream);
 
+/* ---- augmented copies of resident frames --------------------------------- */
+
+/* One variant of a uint8 [H,W,3] frame, the reference's dataset augmentation
+ * (extract_featuressingle.py:49-52,116-120: v2.RandomRotation, v2.RandomSolarize, torchvision
+ * v2's tensor path; that parity is unpinned, the library being absent -- DESIGN.md section 4.2h
+ * holds the definition): the rotation first, then the solarize; either may be off.
+ *   rotation   by `angle` degrees, counter-clockwise for positive angles, about the image centre,
+ *              nearest neighbour, same size, fill 0.  The caller passes c = cos(r), s = sin(r) of
+ *              r = radians(-angle), so no device libm enters.  In fp64, in this order, without
+ *              fused multiply-adds: cx = (W-1)*0.5, cy = (H-1)*0.5; for output pixel (row j,
+ *              column i) dx = i - cx, dy = j - cy, xs = (c*dx + s*dy) + cx,
+ *              ys = ((-s)*dx + c*dy) + cy, xi = rint(xs), yi = rint(ys) (half to even); the
+ *              pixel is src[yi, xi, :] where 0 <= xi < W and 0 <= yi < H, else 0.
+ *   solarize   a byte v becomes 255 - v where v >= threshold; threshold in [0, 256], 256 = off.
+ *              Filled pixels go through it too.
+ *   swap_rb    output channel k is source channel 2 - k (applied at the load, so it commutes
+ *              with both transforms): the RGB -> BGR flip of extract_features_mp.py:124.
+ * An item with everything off is a plain copy of frame `src`. */
+typedef struct {
+  double c, s;          /* cos / sin of radians(-angle); read only when rotate != 0 (finite) */
+  int32_t src;          /* source frame index in [0, n_src)                                  */
+  int32_t rotate;       /* 0 / 1                                                             */
+  int32_t threshold;    /* solarize threshold in [0, 256]; 256 = off                         */
+  int32_t swap_rb;      /* 0 / 1                                                             */
+  int32_t reserved[2];  /* zero                                                              */
+} isl_aug_item;
+
+/* dst[k] = variant(src[items[k].src], items[k]) for k < m, in one launch on `stream`:
+ * d_src uint8 [n_src,H,W,3], d_dst uint8 [m,H,W,3], both on the current device; `items` is a
+ * host array of m records, uploaded stream-ordered through a pinned ring (the call does not
+ * wait for the stream unless eight earlier calls are still in flight).  m == 0 is a no-op.
+ * ISL_E_ARG, before any device work, for: a NULL buffer, n_src, H or W <= 0, H*W > 2^29, m < 0
+ * or m > 65535, a src index outside [0, n_src), a threshold outside [0, 256], rotate or swap_rb
+ * not 0 / 1, a non-finite c or s of a rotating item, a non-zero reserved field, or d_dst
+ * overlapping d_src. */
+int isl_augment(const uint8_t* d_src, int n_src, int H, int W, uint8_t* d_dst,
+                const isl_aug_item* items, int m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

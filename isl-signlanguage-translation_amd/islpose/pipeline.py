@@ -12,7 +12,11 @@ The MI355X counterpart of the reference's feature extractor
   as one CSV per rank (``saveFeaturesDict``, :58-63) and gathered on rank 0
   (the mp.Queue of :204-231, here a host-side gather of a few KB per frame);
 * resume: frames whose JSON already exists are skipped (extract_features.py:97-101);
-* the frame fed to the model is ``frame[:, :, ::-1]`` (RGB video -> BGR, :124).
+* the frame fed to the model is ``frame[:, :, ::-1]`` (RGB video -> BGR, :124);
+* augmented variants (``transforms=``; extract_featuressingle.py:49-52,116-120, commented out
+  in extract_features_mp.py:115-138): each transform's variant of a frame goes through the
+  model like the frame and is filed under ``<stem>-<TransformClassName>/`` with
+  ``transform=<TransformClassName>`` in its row (islpose/augment.py).
 
 What differs, MI355X-first: frames go to the GPU in batches (``ISLSignPos.call_batch``:
 one body launch sequence per batch instead of per frame), every rank pins its
@@ -206,10 +210,20 @@ class KeypointExtractor:
     a copy stream), the RGB -> BGR flip of extract_features_mp.py:124 runs on the GPU,
     and the JSON / feature-row writing runs on a writer thread.  The outputs are the
     same as with overlap=False (the sequential loop: host flip, synchronous upload,
-    inline writes)."""
+    inline writes).
+
+    transforms (None: today's path and outputs, originals only): a list of islpose.augment
+    descriptors, the reference's augmented extraction (extract_featuressingle.py:49-52,116-120).
+    The unit of work is then (frame, 'original' or a transform): resume is tested per unit, a
+    batch holds `batch` units, its distinct source frames go up once, and one launch
+    (islpose.augment.apply; apply_numpy on the host path) builds the batch from them, the
+    RGB -> BGR flip folded in.  A variant's JSON goes to <stem>-<transform.name>/ and its row
+    carries transform=name; frames_done and frames_skipped then count units."""
 
     def __init__(self, model, out_base: str, batch: int = 64, resume: bool = True, write_json: bool = True,
-                 export: bool = True, overlap=None):
+                 export: bool = True, overlap=None, transforms=None):
+        from . import augment
+        self.transforms = None if transforms is None else augment.check_transforms(transforms)
         self.model = model
         self.export = export
         self.out_base = out_base
@@ -232,12 +246,44 @@ class KeypointExtractor:
 
     def _write(self, rows, filename, label_type, expression, ids, feats):
         for idx, feat in zip(ids, feats):
-            p = json_path(self.out_base, label_type, expression, filename, idx)
+            # a unit of the augmented path is (frame index, transform name)
+            idx, name = idx if isinstance(idx, tuple) else (idx, "original")
+            p = json_path(self.out_base, label_type, expression, filename, idx, name)
             if self.write_json:
                 os.makedirs(os.path.dirname(p), exist_ok=True)
                 with open(p, "w") as f:
                     f.write(frame_json(*feat))
-            rows.append(feature_row(p, idx, label_type, expression, feat, export=self.export))
+            rows.append(feature_row(p, idx, label_type, expression, feat, transform=name, export=self.export))
+
+    def _aug_batches(self, videos):
+        """_batches with transforms: per batch ((rows, filename, label_type, expression, units,
+        items), the batch's distinct source frames).  units: [(frame index, name)], frame by
+        frame, the original before the transforms in list order (the reference's loop); items:
+        islpose.augment.Item per unit, indexing the distinct frames."""
+        from . import augment
+        for filename, frames, label_type, expression, rows in videos:
+            if callable(frames):
+                frames = frames()
+            todo = []
+            for idx in range(len(frames)):
+                for k, name in enumerate(["original"] + [t.name for t in self.transforms]):
+                    if self.resume and os.path.exists(json_path(self.out_base, label_type, expression, filename,
+                                                                 idx, name)):
+                        self.frames_skipped += 1
+                        continue
+                    todo.append((idx, k - 1, name))
+            for s in range(0, len(todo), self.batch):
+                part = todo[s:s + self.batch]
+                srcs = sorted({u[0] for u in part})
+                pos = {idx: j for j, idx in enumerate(srcs)}
+                items = [augment.item(pos[idx], None if k < 0 else
+                                      augment.params_for(self.transforms[k], filename, idx, k))
+                         for idx, k, _ in part]
+                if srcs == list(range(srcs[0], srcs[-1] + 1)) and hasattr(frames, "shape"):
+                    sel = frames[srcs[0]:srcs[-1] + 1]
+                else:
+                    sel = np.stack([np.asarray(frames[i]) for i in srcs])
+                yield (rows, filename, label_type, expression, [(idx, name) for idx, _, name in part], items), sel
 
     def _batches(self, videos):
         """videos: iterable of (filename, frames, label_type, expression) -> per batch
@@ -266,6 +312,13 @@ class KeypointExtractor:
         # model keeps numpy BGR batches
         device_ok = hasattr(self.model, "call_batches") or getattr(self.model, "accepts_device_frames", False)
         overlap = (torch.cuda.is_available() and device_ok) if self.overlap is None else self.overlap
+        if not overlap and self.transforms is not None:
+            from . import augment
+            for (rows, filename, lt, ex, units, items), sel in self._aug_batches(vids):
+                bgr = augment.apply_numpy(sel, items, swap_rb=True)
+                self._write(rows, filename, lt, ex, units, self.model.call_batch(bgr))
+                self.frames_done += len(units)
+            return out
         if not overlap:
             for (rows, filename, lt, ex, ids), sel in self._batches(vids):
                 # model(frame[:, :, ::-1]): the reference feeds BGR (extract_features_mp.py:124)
@@ -278,6 +331,13 @@ class KeypointExtractor:
         writer = _Writer(self._write)
 
         def bgr_batches():
+            if self.transforms is not None:
+                from . import augment
+                for meta, rgb in _Prefetch(self._aug_batches(vids), dev):
+                    # the batch's units from its resident source frames, in one launch; swap_rb
+                    # is the flip of extract_features_mp.py:124
+                    yield meta[:5], augment.apply(rgb, meta[5], swap_rb=True)
+                return
             for meta, rgb in _Prefetch(self._batches(vids), dev):
                 yield meta, rgb.flip(-1)                      # extract_features_mp.py:124, on the GPU
 
@@ -299,12 +359,13 @@ class KeypointExtractor:
 
 
 def extract_dataset(rows, decode, model, out_base: str, rank: int = 0, world: int = 1, batch: int = 64,
-                    resume: bool = True, write_json: bool = True, export: bool = True, overlap=None):
+                    resume: bool = True, write_json: bool = True, export: bool = True, overlap=None,
+                    transforms=None):
     """rows: [{'Filepath', 'type', 'expression'}] (the dataset CSV of extract_features_mp.py:187).
     Videos are sharded contiguously across ranks; returns (this rank's feature rows, extractor)."""
     start, end = shard_bounds(len(rows), rank, world)
     ex = KeypointExtractor(model, out_base, batch=batch, resume=resume, write_json=write_json, export=export,
-                           overlap=overlap)
+                           overlap=overlap, transforms=transforms)
     videos = [(r['Filepath'].split('/')[-1], (lambda fp=r['Filepath']: decode(fp)), r['type'], r['expression'])
               for r in rows[start:end]]
     out = []
@@ -327,16 +388,16 @@ def read_dataset_csv(path: str):
 
 
 def run(rows, decode, model, out_base: str, rank: int, world: int, batch: int = 64, resume: bool = True,
-        write_json: bool = True, group=None, export: bool = True, overlap=None):
+        write_json: bool = True, group=None, export: bool = True, overlap=None, transforms=None):
     """One rank's share + the host-side gather; rank 0 writes the combined CSV like the
     reference's __main__ (extract_features_mp.py:225-239). Returns (rows on rank 0 or None, stats)."""
     t0 = time.time()
     feats, ex = extract_dataset(rows, decode, model, out_base, rank, world, batch, resume, write_json, export,
-                                overlap)
+                                overlap, transforms)
     dt = time.time() - t0
     stamp = datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
     save_features_csv(feats, os.path.join(out_base, "output_%d_exectime-%.4f_%s.csv" % (rank, dt, stamp)))
-    tagged = [((r['filepath'], r['frame_no']), r) for r in feats]
+    tagged = [((r['filepath'], r['frame_no']), r) for r in feats]    # (a variant's path names its transform)
     merged = gather_to_rank0(tagged, rank, world, group=group)
     stats = {"rank": rank, "frames": ex.frames_done, "skipped": ex.frames_skipped, "seconds": dt}
     if rank == 0:

@@ -125,7 +125,7 @@ EXPORTS = ["isl_abi_version", "isl_last_error", "isl_net_create", "isl_net_destr
            "isl_net_set_precision", "isl_net_get_precision", "isl_net_set_act_storage",
            "isl_net_get_act_storage", "isl_net_act_storage_active", "isl_post_opts_default",
            "isl_body_post_opts", "isl_hand_post_opts", "isl_hand_post_crops_opts",
-           "isl_net_preprocess_crops_flip", "isl_hand_post_ex", "isl_hand_post_crops_ex"]
+           "isl_net_preprocess_crops_flip", "isl_hand_post_ex", "isl_hand_post_crops_ex", "isl_augment"]
 
 
 class IslCaps(ctypes.Structure):
@@ -150,6 +150,14 @@ class IslCrop(ctypes.Structure):
 class IslPostOpts(ctypes.Structure):
     _fields_ = [("thre1", ctypes.c_double), ("thre2", ctypes.c_double), ("hand_thre", ctypes.c_double),
                 ("max_people", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+class IslAugItem(ctypes.Structure):
+    """isl_aug_item: c, s = cos / sin of radians(-angle); src frame index; rotate 0 / 1; solarize
+    threshold in [0, 256] (256: off); swap_rb 0 / 1; reserved zero."""
+    _fields_ = [("c", ctypes.c_double), ("s", ctypes.c_double), ("src", ctypes.c_int32),
+                ("rotate", ctypes.c_int32), ("threshold", ctypes.c_int32), ("swap_rb", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 2)]
 
 
 def post_opts_struct(opts: dict) -> IslPostOpts:
@@ -225,6 +233,7 @@ def lib():
                                                 ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.isl_hand_post_ex.argtypes = L.isl_hand_post_opts.argtypes + [pu8, vp]
     L.isl_hand_post_crops_ex.argtypes = L.isl_hand_post_crops_opts.argtypes + [pu8, vp]
+    L.isl_augment.argtypes = [vp, i32, i32, i32, vp, ctypes.POINTER(IslAugItem), i32, vp]
     for name in EXPORTS[2:]:
         getattr(L, name).restype = i32
     if L.isl_abi_version() != 1:
@@ -242,6 +251,23 @@ def check(rc: int, what: str = ""):
     if rc == ISL_E_INDEX:
         raise IndexError("list assignment index out of range")
     raise IslError("%s failed (%d): %s" % (what or "libislpose", rc, msg))
+
+
+def augment(src_u8, items, out=None, stream=None):
+    """isl_augment: src_u8 cuda uint8 [n_src, H, W, 3] (contiguous), items a sequence of
+    IslAugItem -> cuda uint8 [len(items), H, W, 3], item k's variant of frame items[k].src, in
+    one launch on `stream` (None: the current stream of the frames' device).  `out`: the
+    destination, which must not overlap the source."""
+    import torch
+    n, H, W, _ = src_u8.shape
+    m = len(items)
+    if out is None:
+        out = torch.empty((m, H, W, 3), dtype=torch.uint8, device=src_u8.device)
+    arr = (IslAugItem * max(m, 1))(*items)
+    with torch.cuda.device(src_u8.device):
+        s = stream if stream is not None else torch.cuda.current_stream(src_u8.device)
+        check(lib().isl_augment(ptr(src_u8), n, H, W, ptr(out), arr, m, ctypes.c_void_p(s.cuda_stream)), "isl_augment")
+    return out
 
 
 def body_layout(kind: int, caps: IslCaps) -> IslLayout:

@@ -25,6 +25,11 @@ scores=float64[21])`` -- the score is the scale-averaged map at the keypoint, 0.
 was not found; without it the result is the reference's 3-tuple.  ``hands_for(frames, body_results)``
 is everything after the body (boxes -> hand peaks -> assembled results) for given body results.
 
+``call_augmented(frames, transforms, keys=None)`` (not a method of the reference class; its
+scripts do this around the model, extract_featuressingle.py:49-52,116-120): the results for the
+frames and for every ``islpose.augment`` transform of them, the variants built on the GPU by one
+launch and everything run as one ``call_batch``.
+
 ``ISLSignPosTranslator(body_model, hand_model, translation_model)`` (:308-443)
 turns a 20-frame window into [1, 20, 156] ``populate_features`` rows and applies
 ``translation_model`` -- a keras-free ``islpose.translate.SignClassifier`` (one
@@ -177,6 +182,34 @@ class ISLSignPos(object):
         else:
             t = torch.from_numpy(np.ascontiguousarray(_as_numpy(frames), dtype=np.uint8)).to("cuda:%d" % body.device)
         return self.hands_for(t, body.estimate(t), (body, hand))
+
+    def call_augmented(self, frames, transforms, keys=None):
+        """The reference's augmented extraction (extract_featuressingle.py:49-52,116-120) for a
+        batch: frames uint8 [n, H, W, 3] BGR (host or cuda), transforms a list of
+        islpose.augment descriptors -> {'original': [...], transform.name: [...]}, each list what
+        call_batch returns for those frames' variants.  The originals and every variant are built
+        by one launch (islpose.augment.apply) from the frames once resident, and run as one
+        call_batch.  keys: one (filename, frame index) per frame for the random transforms'
+        draws (islpose.augment.params_for); None: ('', i) for frame i."""
+        from islpose import augment
+        ts = augment.check_transforms(transforms)
+        ests = self._estimators()
+        if isinstance(frames, torch.Tensor) and frames.is_cuda:
+            t = frames
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(_as_numpy(frames), dtype=np.uint8)).to("cuda:%d" % ests[0].device)
+        if t.dtype != torch.uint8 or t.ndim != 4 or t.shape[3] != 3:
+            raise ValueError("frames: uint8 [n, H, W, 3] expected, got %s %s" % (t.dtype, tuple(t.shape)))
+        n = t.shape[0]
+        keys = [("", i) for i in range(n)] if keys is None else list(keys)
+        if len(keys) != n:
+            raise ValueError("keys needs one (filename, index) per frame: %d keys for %d frames" % (len(keys), n))
+        items = [augment.item(i) for i in range(n)]
+        for k, tr in enumerate(ts):
+            items += [augment.item(i, augment.params_for(tr, keys[i][0], keys[i][1], k)) for i in range(n)]
+        res = self.call_batch(augment.apply(t, items), ests) if n else []
+        names = ["original"] + [tr.name for tr in ts]
+        return {name: res[j * n:(j + 1) * n] for j, name in enumerate(names)}
 
     def hands_for(self, frames_t, body_results, ests=None, defer=False):
         """Everything after the body: frames_t cuda uint8 [n, H, W, 3], body_results

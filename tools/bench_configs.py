@@ -134,14 +134,19 @@ def c4(args):
 def c5(args):
     """configs[4]: the extract_features_mp.py:122-132 pipeline on 1080x1920 RGB frames
     (Mode R body net 184x327 -> 184x328, batched hand crops, per-frame JSON files),
-    sequential vs overlapped (prefetch + async H2D + GPU flip + writer thread)."""
+    sequential vs overlapped (prefetch + async H2D + GPU flip + writer thread).  --augment
+    adds the reference's augmented variants (extract_featuressingle.py:49-52,116-120): the
+    unit of work is then (frame, original-or-transform), each a full model pass, and the
+    *_frames_per_s figures are reported beside *_units_per_s."""
     import shutil
     import tempfile
-    from islpose import pipeline, synth
+    from islpose import augment, pipeline, synth
     from islpose.body import BodyEstimator
     from src.body import Body
     from src.hand import Hand
     from src.ISL_Model_parameter import ISLSignPos
+    transforms = augment.parse_spec(args.augment, seed=args.augment_seed)
+    per_frame = 1 + len(transforms or ())
     T, H, W = args.c5_frames, 1080, 1920
     B = args.c5_batch
     rgb = synth.synth_frames(T, H, W, seed=57)
@@ -159,29 +164,35 @@ def c5(args):
     res = {"config": "C5 video -> per-frame JSON, 1080x1920 RGB frames", "frames": T * len(rows),
            "videos": len(rows), "batch": B, "export": False, "max_people": args.max_people,
            "hand_scales": list(isl.hand_opts["hand_scales"]), "flip_left": bool(args.flip_left),
+           "augment": args.augment or None, "units_per_frame": per_frame,
            "decode": "frames already decoded in host memory (pims/ffmpeg absent); the pipeline reads them as "
                      "slices of the [T,H,W,3] array"}
     for ov in ((True,) if args.c5_overlap_only else (False, True)):
         out = tempfile.mkdtemp(prefix="c5_")
         try:
             # warm-up (arenas, hand scales) on the first video, then the timed pass over all
-            pipeline.extract_dataset(rows[:1], clips.__getitem__, isl, out, batch=B, export=False, overlap=ov)
+            pipeline.extract_dataset(rows[:1], clips.__getitem__, isl, out, batch=B, export=False, overlap=ov,
+                                     transforms=transforms)
             shutil.rmtree(out)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             feats, ex = pipeline.extract_dataset(rows, clips.__getitem__, isl, out, batch=B,
-                                                 export=False, overlap=ov)
+                                                 export=False, overlap=ov, transforms=transforms)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            hands = 0
+            hands = peaks = 0
             for f in feats:
                 hands += len(f["all_hand_peaks"])
+                peaks += len(f["candidate"])
         finally:
             shutil.rmtree(out, ignore_errors=True)
         key = "overlap" if ov else "sequential"
-        res[key + "_frames_per_s"] = round(ex.frames_done / dt, 2)
+        # (the extractor counts units: frames, times 1 + the number of transforms)
+        res[key + "_units_per_s"] = round(ex.frames_done / dt, 2)
+        res[key + "_frames_per_s"] = round(ex.frames_done / per_frame / dt, 2)
         res[key + "_s"] = round(dt, 3)
-        res["hand_crops_per_frame"] = round(hands / max(len(feats), 1), 2)
+        res["hand_crops_per_frame"] = round(hands / max(len(feats), 1), 2)     # (per unit with --augment)
+        res["body_peaks_per_frame"] = round(peaks / max(len(feats), 1), 2)
     return res
 
 
@@ -368,6 +379,10 @@ def main():
     ap.add_argument("--flip-left", action="store_true",
                     help="FRAME / C3 / C5 / HANDS2: mirror left-hand crops before the hand net (C3: every first "
                          "crop of a frame)")
+    ap.add_argument("--augment", default=None,
+                    help="C5: augmented variants per frame, e.g. rotation:30,solarize:192 (RandomRotation / "
+                         "RandomSolarize, islpose.augment.parse_spec); default: none")
+    ap.add_argument("--augment-seed", type=int, default=0, help="C5: seed of the --augment draws")
     a = ap.parse_args()
     a.hand_scales = tuple(float(v) for v in a.hand_scales.split(",")) if a.hand_scales else None
     if a.precision:

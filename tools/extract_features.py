@@ -57,13 +57,21 @@ def main():
     ap.add_argument("--hand-info", action="store_true",
                     help="add a hand_info key to every frame's JSON: per hand its person, is_left, box and the 21 "
                          "keypoint scores (0.0: not found)")
+    ap.add_argument("--augment", default=None,
+                    help="also extract augmented variants of every frame, as the reference's "
+                         "extract_featuressingle.py does: comma-separated rotation:DEGREES (RandomRotation) and "
+                         "solarize:THRESHOLD[:P] (RandomSolarize), e.g. rotation:30,solarize:192; each goes to "
+                         "<stem>-<TransformClassName>/ with its name in the row's transform column")
+    ap.add_argument("--augment-seed", type=int, default=0,
+                    help="seed of the --augment draws (per frame: seed, video name, frame index, position)")
     a = ap.parse_args()
     hand_scales = tuple(float(v) for v in a.hand_scales.split(",")) if a.hand_scales else None
 
     import torch
-    from islpose import pipeline, synth
+    from islpose import augment, pipeline, synth
     from islpose.parallel import dist_env
 
+    transforms = augment.parse_spec(a.augment, seed=a.augment_seed)
     rank, local, world = dist_env()
     group = None
     if world > 1:
@@ -99,8 +107,10 @@ def main():
     t0 = time.time()
     merged, stats = pipeline.run(rows, decode, model, a.out, rank, world, batch=a.batch,
                                  resume=not a.no_resume, write_json=not a.no_json, group=group,
-                                 export=not a.no_export)
-    stats["frames_per_s"] = stats["frames"] / max(time.time() - t0, 1e-9)
+                                 export=not a.no_export, transforms=transforms)
+    # (with --augment the extractor's count is units: frames times 1 + the number of transforms)
+    stats["units_per_frame"] = 1 + len(transforms or ())
+    stats["frames_per_s"] = stats["frames"] / stats["units_per_frame"] / max(time.time() - t0, 1e-9)
     print(json.dumps(stats))
     if world > 1:
         import torch.distributed as dist
