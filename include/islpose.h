@@ -398,6 +398,15 @@ int isl_hand_post_crops_ex(isl_net* net, int n, const int32_t* crop_w, int nscal
  * sums (the block-cooperative device routine): d_out[0] = sum(d_a[0..n)). */
 int isl_debug_np_sum(const double* d_a, int64_t n, double* d_out, void* stream);
 
+/* Diagnostic: one 3x3 convolution layer (stride 1, pad 1, bias, PReLU) of the split-fp16 path on
+ * host arrays, outside any net -- shapes no graph has, such as a K loop of one or two steps.
+ * x [n][cin][h][w], wgt [cout][cin][3][3], bias and slope [cout], y [n][cout][h][w], all fp32 on
+ * the host; cin a multiple of 8.  kernel 0: conv_x3; 1: the Winograd kernel (wino_f16), ISL_E_ARG
+ * when the shape is not eligible for it (cout % 64, >= 32 tiles per row, > 1024 pixels).  The call
+ * is synchronous on the current device; ISL_E_RANGE when the layer left the fp16 split range. */
+int isl_debug_conv3x3(const float* x, int n, int cin, int h, int w, const float* wgt, const float* bias,
+                      const float* slope, int cout, int kernel, float* y);
+
 /* Sign classifier of ISLSignPosTranslator (reference demo_isl_translate.py:72-100,
  * applied in src/ISL_Model_parameter.py:337 to a [1,20,156] window of
  * populate_features rows, :376-443): Masking(0) -> BatchNorm -> BiLSTM(32, seq)

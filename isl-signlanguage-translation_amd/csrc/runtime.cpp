@@ -2473,4 +2473,84 @@ int isl_net_run(isl_net* net, float* d_out0, float* d_out1, void* stream) {
   return copy_outputs(net, d_out0, d_out1, s);
 }
 
+int isl_debug_conv3x3(const float* x, int n, int cin, int h, int w, const float* wgt, const float* bias,
+                      const float* slope, int cout, int kernel, float* y) {
+  if (!x || !wgt || !bias || !slope || !y) return fail(ISL_E_ARG, "isl_debug_conv3x3: NULL argument");
+  if (n <= 0 || n > 64 || cin <= 0 || cin > 1024 || cin % 8 || cout <= 0 || cout > 1024 || h <= 0 || w <= 0 ||
+      (long long)h * w > (1 << 20) || (kernel != 0 && kernel != 1))
+    return fail(ISL_E_ARG, "isl_debug_conv3x3: bad argument");
+  ConvLayer c = mk("debug", cin, cout, 3, ACT_PRELU);
+  c.w.assign(wgt, wgt + (size_t)cout * cin * 9);
+  c.cmap = {{0, 0, cin}};
+  c.cin_phys = cin;
+  c.bco = conv_bco_for(cout);
+  Act in, out;
+  in.n = out.n = n; in.H = out.H = h; in.W = out.W = w; in.pad = out.pad = 1;
+  in.cs = cin; out.cs = round8(cout);
+  // the activations' layout: [n][chunk of 8 channels][h + 2][w + 2][8], a zero ring
+  const int Wp = w + 2;
+  std::vector<float> hin(in.frame_elems() * n, 0.f), hout(out.frame_elems() * n);
+  for (int f = 0; f < n; ++f)
+    for (int ch = 0; ch < cin; ++ch)
+      for (int yy = 0; yy < h; ++yy)
+        for (int xx = 0; xx < w; ++xx)
+          hin[((size_t)f * (cin / 8) + ch / 8) * in.chunk_elems() + ((size_t)(yy + 1) * Wp + xx + 1) * 8 + ch % 8] =
+              x[(((size_t)f * cin + ch) * h + yy) * w + xx];
+  const size_t nb = ((size_t)cout + 255) / 256 * 256 + 256;   // bias / slopes padded to any channel tile
+  std::vector<float> hb(nb, 0.f), hs(nb, 0.f);
+  std::copy(bias, bias + cout, hb.begin());
+  std::copy(slope, slope + cout, hs.begin());
+  float inv = 1.f;
+  const std::vector<_Float16> pk = kernel == 1 && cout % 64 == 0 ? pack_wino_f16(c, &inv) : pack_x3(c, c.bco, &inv);
+  float *d_in = nullptr, *d_out = nullptr, *d_b = nullptr, *d_s = nullptr;
+  void* d_w = nullptr;
+  int* d_flag = nullptr;
+  int flag = 0;
+  auto run = [&]() -> int {
+    HIP_OK(hipMalloc(&d_in, in.bytes()));
+    HIP_OK(hipMalloc(&d_out, out.bytes()));
+    HIP_OK(hipMalloc(&d_b, nb * 4));
+    HIP_OK(hipMalloc(&d_s, nb * 4));
+    HIP_OK(hipMalloc(&d_w, pk.size() * sizeof(_Float16)));
+    HIP_OK(hipMalloc(&d_flag, 4));
+    HIP_OK(hipMemcpy(d_in, hin.data(), in.bytes(), hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(d_out, 0, out.bytes()));
+    HIP_OK(hipMemcpy(d_b, hb.data(), nb * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_s, hs.data(), nb * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_w, pk.data(), pk.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(d_flag, 0, 4));
+    ConvLaunch L;
+    L.in = d_in; L.in_pad = 1; L.in_cs = in.cs; L.in_coff = 0;
+    L.out = d_out; L.out_pad = 1; L.out_cs = out.cs; L.out_coff = 0;
+    L.wpk = nullptr; L.bias = d_b; L.slope = d_s;
+    L.n = n; L.H = h; L.W = w; L.ks = 3; L.cin_chunks = cin / 8;
+    L.cout = cout; L.bco = c.bco; L.act = ACT_PRELU;
+    L.wx3 = d_w; L.wscale_inv = inv; L.range_flag = d_flag;
+    if (kernel == 1) {
+      if (!wino_f16_fits(L)) return fail(ISL_E_ARG, "isl_debug_conv3x3: shape not eligible for the Winograd kernel");
+      HIP_OK(launch_wino_f16(L, 0));
+    } else {
+      if (!x3_fits(L)) return fail(ISL_E_ARG, "isl_debug_conv3x3: shape does not fit conv_x3");
+      HIP_OK(launch_conv_x3(L, 0));
+    }
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(hout.data(), d_out, out.bytes(), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost));
+    return ISL_OK;
+  };
+  const int rc = run();
+  for (void* p : {(void*)d_in, (void*)d_out, (void*)d_b, (void*)d_s, d_w, (void*)d_flag})
+    if (p) (void)hipFree(p);
+  if (rc) return rc;
+  if (flag) return fail(ISL_E_RANGE, "isl_debug_conv3x3: the layer left the fp16 split range");
+  const int Co8 = out.cs / 8;
+  for (int f = 0; f < n; ++f)
+    for (int co = 0; co < cout; ++co)
+      for (int yy = 0; yy < h; ++yy)
+        for (int xx = 0; xx < w; ++xx)
+          y[(((size_t)f * cout + co) * h + yy) * w + xx] =
+              hout[((size_t)f * Co8 + co / 8) * out.chunk_elems() + ((size_t)(yy + 1) * Wp + xx + 1) * 8 + co % 8];
+  return ISL_OK;
+}
+
 }  // extern "C"

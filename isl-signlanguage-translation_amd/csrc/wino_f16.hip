@@ -40,17 +40,25 @@
 //     rows = 32 banks, lane pairs by 16 B).
 //   * A K step is four groups (tile half j, channel quad Q) of six ds_read_b128, 22 VALU and,
 //     behind each Q = 1 group, the 12 MFMAs of j.  The reads run one group ahead of their use:
-//     the first group's at the top of the step, in front of the filter loads and the DMA; the
+//     the first group's at the top of the step; the
 //     next group's as soon as the current group's row combinations are formed and its 24 raw
 //     registers are free.  Reads and their waits are inline asm, tied by operands to the work
 //     they stand behind, so the wait of a group finds its pixels landed behind the previous
 //     group's splits and MFMAs instead of straight behind the reads (what hipcc places).
+//   * The step's 12 vector-memory instructions (8 filter loads of pair k + 1, 4 DMA pieces of pair
+//     k + 2) are spread over the step, one at a time, each inline asm tied between two neighbours:
+//     two filter loads behind the splits of group (0, 0), four behind every second MFMA of the
+//     j = 0 burst, two behind the splits of group (1, 0), the four pieces behind every third MFMA
+//     of the j = 1 burst.  Issued together at the top of the step, behind the barrier, they cost
+//     the eight waves 750-1700 cycles of issue before the first VALU (a quarter of the step,
+//     DESIGN 4.3j).  The filter loads write the idle register set; the counted waits are
+//     vmcnt(6) in front of the first MFMA and vmcnt(12) in front of the barrier.
 //   * Epilogue: the waves' M tiles meet in LDS (two rounds of 32 channels, 128 KB), one
 //     thread per (4 channels, tile) sums them in a fixed order into the 2x2 outputs.
 //
 // Per K step and CU (8 waves of 24 MFMAs): 1536 MFMA cycles per SIMD, 192 KB of LDS reads
 // (24 ds_read_b128 per wave), ~130 VALU per wave and 64 KB of filters + 26 KB of input from
-// L2.  255 VGPRs, no spills, two waves per SIMD.  Eligible launches (wino_f16_fits): 3x3,
+// L2.  242 VGPRs, no spills, two waves per SIMD.  Eligible launches (wino_f16_fits): 3x3,
 // cout % 64 == 0, no fused pool or pooled-input staging, at least 32 tiles per row and > 1024
 // pixels per frame (no canonical K ranges: those layers keep conv_x3's batch-invariant sums).
 #include <algorithm>
@@ -76,6 +84,7 @@ struct W2Args {
   const float* bias;
   const float* slope;
   int* range_flag;
+  unsigned long long* dbg;      // STAMP (development): block 0's s_memtime segment sums, [wave 8][8]
   long long in_fs, in_chs, out_fs, out_chs;   // frame / chunk strides (floats)
   float wscale_inv;             // 2^-s
   int in_pad, out_pad, H, W, TH, TW, pairs, cin_chunks, co_blocks, bpf, act, nblocks;
@@ -121,8 +130,36 @@ __device__ __forceinline__ f32x2 hi2(const f32x4& v) { return f32x2{v.z, v.w}; }
 // libislpose.so has ABL = 0 only.
 // PF: 1 = the raw pixels of a channel quad are read one quad ahead (below), 0 = read where they are
 // used (the development build's reference for interleaved A/B runs).
-template <int ABL, int PF>
+// MV (PF = 1): where a K step issues its 12 vector-memory instructions, the 8 filter loads of pair
+// k + 1 and the 4 DMA pieces of pair k + 2 (w2_slot below).  0 = all at the top of the step, behind
+// the first group's reads (the loop before; development build, tools/convbench "w2t"); 1 = the
+// filter loads behind the first eight MFMAs of the j = 0 burst, the pieces behind every second
+// MFMA of the j = 1 burst; 2 = spread over the whole step: two filter loads behind the splits of
+// each Q = 0 group, four in the j = 0 burst, the pieces in the j = 1 burst; 3 = two pieces behind
+// the splits of each Q = 0 group, four filter loads in each burst.  libislpose.so has W2_MV only.
+// STAMP (development build, tools/convbench with CONVBENCH_W2STAMP=1): s_memtime stamps at eight
+// points of the K step, summed per segment in scalar registers; block 0 stores its sums once,
+// behind the loop.  The stamps fence the scheduler and drain the LDS reads in flight: read the
+// segments' differences between builds, not the run time.
+constexpr int W2_MV = 2;
+// what stands behind MFMA m (0 .. 11) of burst j: -1 nothing, 0 .. 7 filter load n, 8 + e DMA piece e
+constexpr int w2_slot(int mv, int j, int m) {
+  if (mv == 1) return j == 0 ? (m < 8 ? m : -1) : (m < 8 && m % 2 == 0 ? 8 + m / 2 : -1);
+  if (mv == 2) return j == 0 ? (m < 8 && m % 2 == 0 ? 2 + m / 2 : -1) : (m % 3 == 0 ? 8 + m / 3 : -1);
+  if (mv == 3) return m < 8 && m % 2 == 0 ? 4 * j + m / 2 : -1;
+  return -1;
+}
+// what stands behind split s (0, 1) of the Q = 0 group of tile half j
+constexpr int w2_gslot(int mv, int j, int s) { return mv == 2 ? 6 * j + s : mv == 3 ? 8 + 2 * j + s : -1; }
+// The counted waits (derivation at the K loop).  In front of the first MFMA, A(k) landed: the
+// vector-memory instructions younger than A(k)'s last load.  In front of the barrier, raw(k+1)
+// landed: those younger than its last piece.  MV 3 ends a step with filter loads, so its pieces have
+// four more behind them, and its prologue has to drain (there raw(1) has nothing behind it).
+constexpr int w2_wait_a(int mv) { return mv == 0 ? 16 : mv == 1 ? 4 : mv == 2 ? 6 : 2; }
+constexpr int w2_wait_raw(int mv) { return mv == 3 ? 16 : 12; }
+template <int ABL, int PF, int MV = W2_MV, bool STAMP = false>
 __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
+  static_assert(PF == 1 || (MV == 0 && !STAMP), "the issue placements and the stamps are those of the PF = 1 loop");
   // [0, 3 BUF): the raw-input ring; [0, 8192): the M exchange of the epilogue; then the epilogue's
   // bias and PReLU slopes (64 + 64 floats)
   __shared__ f32x4 smem[8192 + 32];
@@ -259,6 +296,47 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
     }
   };
 
+  // MV != 0: one vector-memory instruction of the step, n = 0 .. 7 filter load n of pair k1 into
+  // the idle register set (xi = n >> 2, i, hi|lo), n = 8 + e DMA piece e of pair k2 into ring slot
+  // sl.  t0, t1 are in-out operands the asm does not touch: the values it has to stand behind and
+  // in front of (the accumulator of the MFMA before it and of the one after it, or a split's
+  // fragment dwords).  The DMA is asm as well (M0 = the piece's LDS address), so that it stays put.
+  auto vmem1 = [&](auto nc, f16x8 (&An)[2][2][2], int k1, int k2, int sl, auto& t0, auto& t1) __attribute__((always_inline)) {
+    constexpr int n = decltype(nc)::value;
+    if constexpr (n < 0) {
+    } else if constexpr (n < 8) {
+      if constexpr ((ABL & 4) != 0) return;
+      const f16x8* u = a.upk + ((size_t)(co_b * a.pairs + k1) * 16 + 4 * wr + 2 * cpr + (n >> 2)) * 256;
+      asm volatile("global_load_dwordx4 %0, %3, %4 offset:%5"
+                   : "=v"(An[n >> 2][(n >> 1) & 1][n & 1]), "+v"(t0), "+v"(t1)
+                   : "v"(uvoff), "s"(u), "n"((n & 3) * 1024)
+                   : "memory");
+    } else {
+      if constexpr ((ABL & 8) != 0) return;
+      constexpr int e = n - 8;
+      const int ch = min(2 * k2 + dch[e], a.cin_chunks - 1);
+      const float* src = in_f + (size_t)ch * a.in_chs;
+      const unsigned dv = doff[e];
+      const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(sl * BUF + (w + 8 * e) * 64) * 16u);
+      asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %4"
+                   : "+v"(t0), "+v"(t1)
+                   : "v"(dv), "s"(m0v), "s"(src)
+                   : "memory");   // (M0 is a reserved register: hipcc sets it in front of each use of its own)
+    }
+  };
+  // STAMP: segment i = the time from the stamp before it (in program order) to stamp i
+  unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
+  auto stamp = [&](int i) __attribute__((always_inline)) {
+    if constexpr (STAMP) {
+      __builtin_amdgcn_sched_barrier(0);
+      unsigned long long t;
+      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+      if (i >= 0) tsum[i] += t - tprev;
+      tprev = t;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
   f32x16 acc[2][2][2];   // [xi][i][j]
 #pragma unroll
   for (int x = 0; x < 2; ++x)
@@ -315,7 +393,9 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
                    : "memory");
 #undef W2_READS
   };
-  auto compute_pf = [&](const f16x8 (&A)[2][2][2], int sl, W2Raw r) __attribute__((always_inline)) {
+  // An, k1, k2, sl2 (MV != 0): the idle filter register set and what the step loads -- the filters
+  // of pair k1 into An, the raw input of pair k2 into ring slot sl2
+  auto compute_pf = [&](f16x8 (&A)[2][2][2], int sl, W2Raw r, f16x8 (&An)[2][2][2], int k1, int k2, int sl2) __attribute__((always_inline)) {
     unsigned Bd[2][2][4];   // [xi][hi|lo] x 4 dwords, quad Q in dwords 2Q, 2Q + 1
     auto group = [&](auto jc, auto qc) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value, Q = decltype(qc)::value;
@@ -356,6 +436,11 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
       const f32x2 v10 = pk_fma_s(sz2, t[4], t[2]), v11 = pk_fma_s(sz2, t[5], t[3]);
       split_dw(f32x4{v00.x, v00.y, v01.x, v01.y}, Bd[0][0][2 * Q], Bd[0][0][2 * Q + 1], Bd[0][1][2 * Q], Bd[0][1][2 * Q + 1]);
       split_dw(f32x4{v10.x, v10.y, v11.x, v11.y}, Bd[1][0][2 * Q], Bd[1][0][2 * Q + 1], Bd[1][1][2 * Q], Bd[1][1][2 * Q + 1]);
+      if constexpr (Q == 0 && MV != 0) {
+        // behind the group's two splits (tied to their hi dwords)
+        vmem1(std::integral_constant<int, w2_gslot(MV, j, 0)>{}, An, k1, k2, sl2, Bd[0][0][0], Bd[0][0][1]);
+        vmem1(std::integral_constant<int, w2_gslot(MV, j, 1)>{}, An, k1, k2, sl2, Bd[1][0][0], Bd[1][0][1]);
+      }
       if constexpr (Q == 1) {
         f16x8 Bh[2], Bl[2];
 #pragma unroll
@@ -363,15 +448,53 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
           Bh[x] = __builtin_bit_cast(f16x8, u32x4{Bd[x][0][0], Bd[x][0][1], Bd[x][0][2], Bd[x][0][3]});
           Bl[x] = __builtin_bit_cast(f16x8, u32x4{Bd[x][1][0], Bd[x][1][1], Bd[x][1][2], Bd[x][1][3]});
         }
+        if constexpr (MV != 0 && j == 0) {
+          // A(k) landed (MV = 0: at the top of the step): the filter loads of this step stand
+          // behind this wait, except those w2_gslot puts into group (0, 0)
+          if constexpr (STAMP) stamp(1);
+          if constexpr ((ABL & 4) == 0)
+            asm volatile("s_waitcnt vmcnt(%8)"
+                         : "+v"(A[0][0][0]), "+v"(A[0][0][1]), "+v"(A[0][1][0]), "+v"(A[0][1][1]), "+v"(A[1][0][0]),
+                           "+v"(A[1][0][1]), "+v"(A[1][1][0]), "+v"(A[1][1][1])
+                         : "n"(w2_wait_a(MV))
+                         : "memory");
+          if constexpr (STAMP) stamp(2);
+        }
+        if constexpr (STAMP) stamp(j == 0 ? 3 : 5);
+        if constexpr (MV == 0) {
 #pragma unroll
-        for (int x = 0; x < 2; ++x)
+          for (int x = 0; x < 2; ++x)
 #pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            if constexpr ((ABL & 1) != 0) continue;
-            acc[x][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[x][i][0], Bh[x], acc[x][i][j], 0, 0, 0);
-            acc[x][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[x][i][0], Bl[x], acc[x][i][j], 0, 0, 0);
-            acc[x][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[x][i][1], Bh[x], acc[x][i][j], 0, 0, 0);
-          }
+            for (int i = 0; i < 2; ++i) {
+              if constexpr ((ABL & 1) != 0) continue;
+              acc[x][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[x][i][0], Bh[x], acc[x][i][j], 0, 0, 0);
+              acc[x][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[x][i][0], Bl[x], acc[x][i][j], 0, 0, 0);
+              acc[x][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[x][i][1], Bh[x], acc[x][i][j], 0, 0, 0);
+            }
+        } else {
+          // The same three MFMAs per accumulator in the same order, written out in the order hipcc
+          // issues them above (per xi the two chains i = 0, 1 alternately), each followed by what
+          // w2_slot puts behind it, tied to its accumulator and to that of the MFMA after it.
+          auto half = [&](auto xc) __attribute__((always_inline)) {
+            constexpr int x = decltype(xc)::value;
+            auto mf = [&](auto mc, auto ic, const f16x8& af, const f16x8& bf, f32x16& nxt) __attribute__((always_inline)) {
+              constexpr int m = decltype(mc)::value, i = decltype(ic)::value;
+              if constexpr ((ABL & 1) == 0) acc[x][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc[x][i][j], 0, 0, 0);
+              vmem1(std::integral_constant<int, w2_slot(MV, j, 6 * x + m)>{}, An, k1, k2, sl2, acc[x][i][j], nxt);
+            };
+            using I0 = std::integral_constant<int, 0>;
+            using I1 = std::integral_constant<int, 1>;
+            mf(std::integral_constant<int, 0>{}, I0{}, A[x][0][0], Bh[x], acc[x][1][j]);
+            mf(std::integral_constant<int, 1>{}, I1{}, A[x][1][0], Bh[x], acc[x][0][j]);
+            mf(std::integral_constant<int, 2>{}, I0{}, A[x][0][0], Bl[x], acc[x][1][j]);
+            mf(std::integral_constant<int, 3>{}, I1{}, A[x][1][0], Bl[x], acc[x][0][j]);
+            mf(std::integral_constant<int, 4>{}, I0{}, A[x][0][1], Bh[x], acc[x][1][j]);
+            mf(std::integral_constant<int, 5>{}, I1{}, A[x][1][1], Bh[x], acc[1][0][j]);   // (xi 1: none follows)
+          };
+          half(std::integral_constant<int, 0>{});
+          half(std::integral_constant<int, 1>{});
+        }
+        if constexpr (STAMP) stamp(j == 0 ? 4 : 6);
       }
     };
     group(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
@@ -432,36 +555,50 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
 
   // K loop, one step per chunk pair k, one barrier per step.  Per step each wave issues the
   // filters of pair k + 1 (8 loads, into the other register set) and the raw input of pair k + 2
-  // (4 LDS-DMA pieces, ring slot (k + 2) % 3), then transforms and multiplies pair k.  Counted
-  // waits (loads past the last pair repeat it, so the counts are the same on every step):
-  //   before the MFMAs: A(k) landed       -- younger: raw(k+1) 4, A(k+1) 8, raw(k+2) 4 -> vmcnt(16)
-  //   before the barrier: raw(k+1) landed -- younger: A(k+1) 8, raw(k+2) 4           -> vmcnt(12)
+  // (4 LDS-DMA pieces, ring slot (k + 2) % 3) while it transforms and multiplies pair k.  At the
+  // top of a step the wave's queue holds A(k) 8, raw(k+1) 4, in that order (the prologue leaves
+  // it so), and every placement issues all of A(k+1) before raw(k+2).  Ring slot (k + 2) % 3 was
+  // last read in step k - 1, behind whose barrier the step stands: a piece is safe anywhere in it.
+  // Counted waits (loads past the last pair repeat it, so the counts are the same on every step):
+  //   before the first MFMA: A(k) landed -- younger: raw(k+1) 4 and what the step has issued by
+  //     then: MV 0 all 12 -> vmcnt(16); MV 1 nothing -> vmcnt(4); MV 2 two loads -> vmcnt(6)
+  //   before the barrier: raw(k+1) landed -- younger: A(k+1) 8, raw(k+2) 4 -> vmcnt(12)
+  // The registers of A(k+1) are idle from the last MFMA of step k - 1 to the load that writes them.
   f16x8 AS[2][2][2][2];   // two register sets [set][xi][i][hi|lo]
   load_a(AS[0], 0);
   dma(0, 0);
   dma(min(1, a.pairs - 1), 1);
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // raw(0) landed (raw(1) may not)
+  if constexpr (MV == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // raw(0) landed (raw(1) may not)
   __syncthreads();                                       // (and the epilogue constants are staged)
   __builtin_amdgcn_sched_barrier(0);
   auto step = [&](int k, f16x8 (&A)[2][2][2], f16x8 (&An)[2][2][2]) __attribute__((always_inline)) {
     W2Raw r0;
+    const int k1 = min(k + 1, a.pairs - 1), k2 = min(k + 2, a.pairs - 1);
+    stamp(0);
     if constexpr (PF != 0) rd(r0, k % 3, 0, std::integral_constant<int, 0>{}, nullptr);
-    load_a(An, min(k + 1, a.pairs - 1));
-    dma(min(k + 2, a.pairs - 1), (k + 2) % 3);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr ((ABL & 4) == 0)
-      asm volatile("s_waitcnt vmcnt(16)"
-                   : "+v"(A[0][0][0]), "+v"(A[0][0][1]), "+v"(A[0][1][0]), "+v"(A[0][1][1]), "+v"(A[1][0][0]),
-                     "+v"(A[1][0][1]), "+v"(A[1][1][0]), "+v"(A[1][1][1])
-                   :
-                   : "memory");
-    if constexpr (PF != 0) compute_pf(A, k % 3, r0);
+    if constexpr (MV == 0) {
+      load_a(An, k1);
+      dma(k2, (k + 2) % 3);
+      __builtin_amdgcn_sched_barrier(0);
+      stamp(1);
+      if constexpr ((ABL & 4) == 0)
+        asm volatile("s_waitcnt vmcnt(16)"
+                     : "+v"(A[0][0][0]), "+v"(A[0][0][1]), "+v"(A[0][1][0]), "+v"(A[0][1][1]), "+v"(A[1][0][0]),
+                       "+v"(A[1][0][1]), "+v"(A[1][1][0]), "+v"(A[1][1][1])
+                     :
+                     : "memory");
+      stamp(2);
+    }
+    if constexpr (PF != 0) compute_pf(A, k % 3, r0, An, k1, k2, (k + 2) % 3);
     else compute(A, k % 3);
     __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" : : "n"(w2_wait_raw(MV)) : "memory");
+    stamp(7);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   };
+  stamp(-1);
   for (int k = 0; k < a.pairs; k += 2) {
     step(k, AS[0], AS[1]);
     if (k + 1 < a.pairs) step(k + 1, AS[1], AS[0]);
@@ -476,6 +613,11 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
                :
                : "memory");
   __syncthreads();
+  if constexpr (STAMP) {
+    if (blockIdx.x == 0 && lane == 0)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) a.dbg[w * 8 + i] = tsum[i];
+  }
 
   bool bad = false;
   if constexpr ((ABL & 16) != 0) {
@@ -601,24 +743,37 @@ hipError_t launch_wino_f16(const ConvLaunch& c, hipStream_t s) {
   if (nb <= 0 || nb > 0x7fffffff) { set_error("wino_f16: bad grid"); return hipErrorInvalidValue; }
   a.nblocks = (int)nb;
 #ifdef ISLPOSE_DEV
-  // ablations 1 .. 31 are those of the PF = 0 loop; ISLPOSE_W2_PF=0 runs that loop whole
+  // ablations 1 .. 31 are those of the PF = 0 loop, 32 and 64 + k those of the PF = 1 loop with its
+  // loads at the top of the step (MV = 0); ISLPOSE_W2_PF=0 runs the PF = 0 loop whole
   const int abl = getenv("ISLPOSE_W2_ABL") ? atoi(getenv("ISLPOSE_W2_ABL")) : 0;
   switch (abl) {
-#define W2ABL(k) case k: hipLaunchKernelGGL((wino_f16<k, 0>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+#define W2ABL(k) case k: hipLaunchKernelGGL((wino_f16<k, 0, 0>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
     W2ABL(1) W2ABL(2) W2ABL(3) W2ABL(4) W2ABL(6) W2ABL(8) W2ABL(12) W2ABL(14) W2ABL(16) W2ABL(31)
 #undef W2ABL
-    case 65: hipLaunchKernelGGL((wino_f16<1, 1>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
-    case 68: hipLaunchKernelGGL((wino_f16<4, 1>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
-    case 72: hipLaunchKernelGGL((wino_f16<8, 1>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
-    case 76: hipLaunchKernelGGL((wino_f16<12, 1>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
-    case 80: hipLaunchKernelGGL((wino_f16<16, 1>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
-    case 32: hipLaunchKernelGGL((wino_f16<32, 1>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+    case 65: hipLaunchKernelGGL((wino_f16<1, 1, 0>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+    case 68: hipLaunchKernelGGL((wino_f16<4, 1, 0>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+    case 72: hipLaunchKernelGGL((wino_f16<8, 1, 0>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+    case 76: hipLaunchKernelGGL((wino_f16<12, 1, 0>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+    case 80: hipLaunchKernelGGL((wino_f16<16, 1, 0>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
+    case 32: hipLaunchKernelGGL((wino_f16<32, 1, 0>), dim3(a.nblocks), dim3(512), 0, s, a); return hipGetLastError();
     default: break;
   }
   if (getenv("ISLPOSE_W2_PF") && atoi(getenv("ISLPOSE_W2_PF")) == 0) {
-    hipLaunchKernelGGL((wino_f16<0, 0>), dim3(a.nblocks), dim3(512), 0, s, a);
+    hipLaunchKernelGGL((wino_f16<0, 0, 0>), dim3(a.nblocks), dim3(512), 0, s, a);
     return hipGetLastError();
   }
+  // ISLPOSE_W2_MV=0 .. 3: where the step issues its loads (default W2_MV); with c.dbg the stamped build
+  const int mv = getenv("ISLPOSE_W2_MV") ? atoi(getenv("ISLPOSE_W2_MV")) : W2_MV;
+  a.dbg = c.dbg;
+  if (mv < 0 || mv > 3) { set_error("wino_f16: ISLPOSE_W2_MV out of range"); return hipErrorInvalidValue; }
+#define W2MV(m)                                                                                    \
+  if (mv == m) {                                                                                   \
+    if (c.dbg) hipLaunchKernelGGL((wino_f16<0, 1, m, true>), dim3(a.nblocks), dim3(512), 0, s, a);  \
+    else hipLaunchKernelGGL((wino_f16<0, 1, m>), dim3(a.nblocks), dim3(512), 0, s, a);             \
+    return hipGetLastError();                                                                      \
+  }
+  W2MV(0) W2MV(1) W2MV(2) W2MV(3)
+#undef W2MV
 #endif
   hipLaunchKernelGGL((wino_f16<0, 1>), dim3(a.nblocks), dim3(512), 0, s, a);
   return hipGetLastError();

@@ -125,7 +125,8 @@ EXPORTS = ["isl_abi_version", "isl_last_error", "isl_net_create", "isl_net_destr
            "isl_net_set_precision", "isl_net_get_precision", "isl_net_set_act_storage",
            "isl_net_get_act_storage", "isl_net_act_storage_active", "isl_post_opts_default",
            "isl_body_post_opts", "isl_hand_post_opts", "isl_hand_post_crops_opts",
-           "isl_net_preprocess_crops_flip", "isl_hand_post_ex", "isl_hand_post_crops_ex", "isl_augment"]
+           "isl_net_preprocess_crops_flip", "isl_hand_post_ex", "isl_hand_post_crops_ex", "isl_augment",
+           "isl_debug_conv3x3"]
 
 
 class IslCaps(ctypes.Structure):
@@ -234,12 +235,32 @@ def lib():
     L.isl_hand_post_ex.argtypes = L.isl_hand_post_opts.argtypes + [pu8, vp]
     L.isl_hand_post_crops_ex.argtypes = L.isl_hand_post_crops_opts.argtypes + [pu8, vp]
     L.isl_augment.argtypes = [vp, i32, i32, i32, vp, ctypes.POINTER(IslAugItem), i32, vp]
+    L.isl_debug_conv3x3.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]
     for name in EXPORTS[2:]:
         getattr(L, name).restype = i32
     if L.isl_abi_version() != 1:
         raise ImportError("libislpose ABI mismatch")
     _lib = L
     return L
+
+
+def debug_conv3x3(x, weight, bias, slope, kernel: str):
+    """One 3x3 layer (pad 1, bias, PReLU) of the split-fp16 path on host arrays (isl_debug_conv3x3):
+    x [n, cin, h, w], weight [cout, cin, 3, 3], bias and slope [cout]; kernel "x3" (conv_x3) or
+    "wino2" (wino_f16).  Returns y [n, cout, h, w] (numpy fp32)."""
+    import numpy as np
+    x, weight, bias, slope = (np.ascontiguousarray(a, np.float32) for a in (x, weight, bias, slope))
+    n, cin, h, w = x.shape
+    cout = weight.shape[0]
+    if weight.shape != (cout, cin, 3, 3) or bias.shape != (cout,) or slope.shape != (cout,):
+        raise ValueError("debug_conv3x3: weight [cout, cin, 3, 3], bias [cout], slope [cout] expected")
+    if kernel not in ("x3", "wino2"):
+        raise ValueError("debug_conv3x3: kernel is 'x3' or 'wino2'")
+    y = np.empty((n, cout, h, w), np.float32)
+    check(lib().isl_debug_conv3x3(x.ctypes.data, n, cin, h, w, weight.ctypes.data, bias.ctypes.data,
+                                  slope.ctypes.data, cout, 1 if kernel == "wino2" else 0, y.ctypes.data),
+          "isl_debug_conv3x3")
+    return y
 
 
 def check(rc: int, what: str = ""):

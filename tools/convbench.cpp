@@ -101,6 +101,12 @@ int main(int argc, char** argv) {
     CK(hipMemset(dbg, 0, wr_blocks * 8 * 8));
     L.dbg = dbg;
   }
+  // CONVBENCH_W2STAMP=1: segment sums of wino_f16's K step (block 0, 8 waves x 8 segments)
+  unsigned long long* w2dbg = nullptr;
+  if (getenv("CONVBENCH_W2STAMP") && atoi(getenv("CONVBENCH_W2STAMP"))) {
+    CK(hipMalloc(&w2dbg, 64 * 8));
+    CK(hipMemset(w2dbg, 0, 64 * 8));
+  }
   const double flops = 2.0 * cout * cin * ks * ks * (double)H * W * n;
   // the polluter of CONVBENCH_POLLUTE: a 1x1 layer on the same buffers (cin chunks of this
   // shape, 32 output channels), default variant
@@ -148,9 +154,18 @@ int main(int argc, char** argv) {
         // w2: the split-fp16 Winograd kernel wino_f16 (ISLPOSE_W2_ABL: its timing ablations)
         // w2o: the same kernel with the raw pixels read where they are used (ISLPOSE_W2_PF=0, the
         // loop before the one-group-ahead reads), for interleaved A/B against w2
-        if ((a == "w2" || a == "w2o") && ww && wino_f16_fits(c)) {
+        // w2t, w2a, w2b, w2c: the loop with its filter loads and DMA at the top of the step (the
+        // loop before they moved), in the MFMA bursts, spread over the whole step, and with the
+        // DMA behind the Q = 0 groups (ISLPOSE_W2_MV=0 .. 3); w2 is the library's placement.
+        // CONVBENCH_W2STAMP=1: the stamped builds of these (segment table below; their run time
+        // is not the kernel's)
+        const bool w2mv = a == "w2t" || a == "w2a" || a == "w2b" || a == "w2c";
+        if ((a == "w2" || a == "w2o" || w2mv) && ww && wino_f16_fits(c)) {
           setenv("ISLPOSE_W2_PF", a == "w2o" ? "0" : "1", 1);
+          if (!w2mv) unsetenv("ISLPOSE_W2_MV");
+          else setenv("ISLPOSE_W2_MV", a == "w2t" ? "0" : a == "w2a" ? "1" : a == "w2b" ? "2" : "3", 1);
           c.wx3 = ww;
+          c.dbg = a == "w2o" ? nullptr : w2dbg;
           return launch_wino_f16(c, 0);
         }
         return hipErrorNotSupported;
@@ -182,9 +197,30 @@ int main(int argc, char** argv) {
         CK(hipEventElapsedTime(&ms, e0, e1));
       }
       const double us = ms * 1e3 / iters;
-      const double fac = (a == "x3" || a == "x3f" || a == "x3m" || a == "x3h" || a == "x3p" || a == "x3d") ? 3.0 : (a == "wx3" || a == "w2" || a == "w2o") ? 3.0 * 16 / 36 : a == "wino" ? 16.0 / 36 : 1.0;
+      const double fac = (a == "x3" || a == "x3f" || a == "x3m" || a == "x3h" || a == "x3p" || a == "x3d") ? 3.0 : (a == "wx3" || a.rfind("w2", 0) == 0) ? 3.0 * 16 / 36 : a == "wino" ? 16.0 / 36 : 1.0;
       printf("  round %d %-7s %9.1f us  fp32-equiv %7.1f TF  alg-MFMA %7.1f TF\n", r, a.c_str(), us,
              flops / us / 1e6, fac * flops / us / 1e6);
+      if (w2dbg && a.rfind("w2", 0) == 0 && a != "w2o") {
+        // cycles per K step, mean over the steps of the last launch: segment i runs from the stamp
+        // before it to stamp i.  w2t: 0 barrier, 1 issue of the 12 loads, 2 wait for A(k), 3 groups
+        // (0,0) and (0,1), 4 burst j = 0, 5 groups (1,0) and (1,1), 6 burst j = 1, 7 wait for
+        // raw(k+1).  w2a, w2b: 1 the groups (0,0) and (0,1), 2 the wait for A(k), 3 nothing (one
+        // stamp's own cost); the rest as w2t
+        unsigned long long h[64];
+        CK(hipMemcpy(h, w2dbg, sizeof h, hipMemcpyDeviceToHost));
+        double mean[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tot = 0;
+        for (int w = 0; w < 8; ++w) {
+          printf("    %-4s wave %d:", a.c_str(), w);
+          for (int i = 0; i < 8; ++i) {
+            printf(" %7.0f", (double)h[w * 8 + i] / pairs);
+            mean[i] += (double)h[w * 8 + i] / pairs / 8;
+          }
+          printf("\n");
+        }
+        printf("    %-4s mean  :", a.c_str());
+        for (int i = 0; i < 8; ++i) printf(" %7.0f", mean[i]), tot += mean[i];
+        printf("  step %.0f\n", tot);
+      }
     }
   }
   if (dbg && wrstamp) {
