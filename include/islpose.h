@@ -407,6 +407,95 @@ int isl_debug_np_sum(const double* d_a, int64_t n, double* d_out, void* stream);
 int isl_debug_conv3x3(const float* x, int n, int cin, int h, int w, const float* wgt, const float* bias,
                       const float* slope, int cout, int kernel, float* y);
 
+/* Diagnostic: one convolution layer on any of the conv kernels, on host arrays, outside any net,
+ * synchronous on the current device -- the per-layer entry of the test suite (tests/
+ * test_gpu_conv_layers.py).  It builds the buffers a net would give the launch (rings, channel
+ * slices, a channel map of segments), runs the launcher the descriptor names and reports, beside
+ * the result, what the launch wrote outside its footprint.
+ *
+ *   x      [n][cin][h][w] fp32, logical channel order; with `vin` the pre-pool map [n][cin][2h][2w]
+ *   wgt    [cout][cin][ks][ks], bias [cout], slope [cout] (PReLU only; NULL otherwise)
+ *   y      [n][cout][h][w]; with `hpool` the pair-max map [n][cout][h][w/2]
+ *   y_pool with `hpool`: [n][cout][h/2][w/2], the map launch_vpool2 makes of it (floor mode); else NULL
+ *
+ * Buffers.  The input buffer has in_cs physical channels in 8-channel chunks and a ring of in_pad
+ * pixels; the layer reads channels [in_coff, in_coff + P), P = the segments' extent rounded up to 8.
+ * Segment i puts logical channels [logical, logical + len) at physical offset phys inside that
+ * span (the cmap of a concat buffer: 52 PAF channels in a 56-channel slot, then 128 features).
+ * Rings and gap channels of the layer's own chunks are zero, as plan() leaves them; every other
+ * chunk, and a slack (a chunk plane + 1024 pixels) on either side of the buffer, holds a NaN
+ * (payload 0x51d1d1), so a
+ * kernel that reads them shows it in its result.  The output buffer has out_cs channels and a ring
+ * of out_pad; the layer writes (frame interior) x [out_coff, out_coff + cout).  Before the launch
+ * the whole buffer and the same slack on either side hold a canary no layer can produce (the quiet
+ * NaN 0x7fc5a5a5, fp16 0x7e5a); after it every element outside the footprint whose bits differ
+ * counts as a stray write -- rings, channels [cout, round8(cout)), other slices, the slack.
+ * With `act16` the input and output buffers hold fp16 (x rounded to nearest even by the entry; the
+ * rgb kernel reads its fp32 input as ever); y is returned as fp32.  With `vin` the entry builds the
+ * pool's pair-max buffer [n][chunk][2h][w][8] (max of horizontal pairs, exact) and the launch stages
+ * from it.  With `hpool` the launch writes the unpadded pair-max buffer (checked as above); the
+ * entry then zeroes that buffer's gap channels (the arena's one-time zeroing) and runs
+ * launch_vpool2 into a canary-filled buffer of ring out_pad, whose footprint is whole chunks:
+ * gap lanes there must read +0.
+ *
+ * ISL_E_ARG: a malformed descriptor, a shape the named kernel does not take (x3_fits,
+ * wino_f16_fits, x3_rgb_fits, x3_hpool_ok, x3_vin_ok, x3_act16_ok, wino_bco_for), or a call over
+ * the limits (n <= 256, h * w <= 2^20, channels <= 1024, each buffer <= 256 MiB).
+ * ISL_E_RANGE only when range_error != 0 and the layer raised the range flag.
+ *
+ * Not reachable here: the fused conv1_1 -> conv1_2 launch, the fused 1x1 pair and the split-K
+ * fold.  The suite holds them bit for bit to their unfused forms at net level
+ * (tests/test_gpu_fused.py, tests/test_gpu_fp16_fused.py); the unfused forms are checked here. */
+enum isl_debug_kernel {
+  ISL_DBG_X3 = 0,      /* launch_conv_x3: the dispatcher picks the variant          */
+  ISL_DBG_WINO2 = 1,   /* launch_wino_f16                                           */
+  ISL_DBG_DIRECT = 2,  /* launch_conv (fp32 matrix cores; the range guard's fallback) */
+  ISL_DBG_WINO = 3,    /* launch_wino (fp32 Winograd)                               */
+  ISL_DBG_RGB = 4      /* launch_conv_x3_rgb (cin = 3)                              */
+};
+
+typedef struct {
+  int32_t phys, logical, len;
+} isl_debug_seg;
+
+typedef struct {
+  int32_t n, h, w;                 /* frames; the plane the convolution runs on               */
+  int32_t cin, cout;               /* logical channels                                        */
+  int32_t ks;                      /* 1, 3, 7                                                 */
+  int32_t act;                     /* 0 none, 1 ReLU, 2 PReLU                                 */
+  int32_t kernel;                  /* enum isl_debug_kernel                                   */
+  int32_t f16;                     /* one-term products (ConvLaunch::f16, hi-only filters)    */
+  int32_t act16;                   /* fp16 buffers (ConvLaunch::act16); needs f16             */
+  int32_t allow_split;             /* 0 / 1: canonical K ranges, with a split-K workspace     */
+  int32_t in_pad, out_pad;         /* rings: 1 or 3, in_pad >= ks / 2                         */
+  int32_t in_cs, in_coff;          /* input buffer channels, the layer's offset (multiples of 8) */
+  int32_t out_cs, out_coff;        /* output buffer channels, the layer's offset              */
+  int32_t nseg;                    /* 1..4                                                    */
+  isl_debug_seg seg[4];
+  int32_t hpool, vin;              /* conv_x3 only                                            */
+  int32_t range_error;             /* != 0: a raised range flag returns ISL_E_RANGE           */
+  int32_t reserved[7];             /* zero                                                    */
+} isl_debug_conv_desc;
+
+typedef struct {
+  int32_t variant;       /* x3_last_variant() (x3, rgb); for wino2 the code the runtime gives  */
+                         /* launch_wino_f16 (a constant: that launcher has no variants and is  */
+                         /* called directly); 0 for direct / wino                              */
+  int32_t range_flag;    /* the launch's range flag as a value                                */
+  int64_t stray_writes;  /* elements outside the footprint whose bits changed                 */
+  int64_t unwritten;     /* footprint elements still holding the canary                       */
+  int32_t stray_stage;   /* the first stray write: 0 the conv's output buffer, 1 the pooled   */
+  int32_t stray_frame;   /*   map; frame -1 = the slack before (chunk -1) or after (chunk 1)  */
+  int32_t stray_chunk;   /*   the buffer, x then counting elements; y, x relative to the      */
+  int32_t stray_y;       /*   frame interior (negative or >= the size: the ring)              */
+  int32_t stray_x;
+  int32_t stray_lane;
+  int32_t reserved[6];
+} isl_debug_conv_result;
+
+int isl_debug_conv(const isl_debug_conv_desc* desc, const float* x, const float* wgt, const float* bias,
+                   const float* slope, float* y, float* y_pool, isl_debug_conv_result* result);
+
 /* Sign classifier of ISLSignPosTranslator (reference demo_isl_translate.py:72-100,
  * applied in src/ISL_Model_parameter.py:337 to a [1,20,156] window of
  * populate_features rows, :376-443): Masking(0) -> BatchNorm -> BiLSTM(32, seq)

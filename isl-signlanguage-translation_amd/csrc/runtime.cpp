@@ -2473,84 +2473,329 @@ int isl_net_run(isl_net* net, float* d_out0, float* d_out1, void* stream) {
   return copy_outputs(net, d_out0, d_out1, s);
 }
 
+// ---- isl_debug_conv: one layer on host arrays, with an output canary and an input poison ----
+
+namespace {
+
+constexpr uint32_t DBG_CANARY32 = 0x7fc5a5a5u;   // quiet NaNs with payloads: no layer produces them
+constexpr uint16_t DBG_CANARY16 = 0x7e5au;
+constexpr uint32_t DBG_POISON32 = 0x7fd1d1d1u;
+constexpr uint16_t DBG_POISON16 = 0x7f1du;
+
+// Host image of an activation buffer (isl::Act layout) of 4- or 2-byte elements with a chunk
+// plane and 1024 pixels of slack on either side.
+struct DbgBuf {
+  Act a;
+  size_t slack = 0;
+  std::vector<uint8_t> h;
+  void* d = nullptr;
+  size_t elems() const { return 2 * slack + a.frame_elems() * a.n; }
+  size_t bytes() const { return elems() * a.esize; }
+  void init(int n, int H, int W, int pad, int cs, int esize) {
+    a.n = n; a.H = H; a.W = W; a.pad = pad; a.cs = cs; a.esize = esize;
+    slack = a.chunk_elems() + 8192;   // more than the longest staged run of any tile (576 pixels)
+  }
+  void alloc() { h.assign(bytes(), 0); }   // (after the caller's size check)
+  void fill(size_t i0, size_t cnt, uint32_t b32, uint16_t b16) {
+    if (a.esize == 4) { uint32_t* p = (uint32_t*)h.data(); std::fill(p + i0, p + i0 + cnt, b32); }
+    else { uint16_t* p = (uint16_t*)h.data(); std::fill(p + i0, p + i0 + cnt, b16); }
+  }
+  size_t chunk_at(int f, int chunk) const { return slack + ((size_t)f * (a.cs / 8) + chunk) * a.chunk_elems(); }
+  size_t at(int f, int ch, int y, int x) const {
+    return chunk_at(f, ch / 8) + ((size_t)(y + a.pad) * (a.W + 2 * a.pad) + x + a.pad) * 8 + ch % 8;
+  }
+  void put(size_t i, float v) {
+    if (a.esize == 4) ((float*)h.data())[i] = v;
+    else ((_Float16*)h.data())[i] = (_Float16)v;   // round to nearest even
+  }
+  float get(size_t i) const { return a.esize == 4 ? ((const float*)h.data())[i] : (float)((const _Float16*)h.data())[i]; }
+  uint32_t bits(size_t i) const { return a.esize == 4 ? ((const uint32_t*)h.data())[i] : ((const uint16_t*)h.data())[i]; }
+  void* dev() const { return (uint8_t*)d + slack * a.esize; }   // the buffer proper
+};
+
+// Counts the elements of `b` outside (frame interior) x [c0, c1) whose bits differ from the canary
+// (where zero_c0 <= channel < c1 inside the footprint: from +0 instead), and the footprint's
+// elements that still hold it.
+static void dbg_scan(const DbgBuf& b, int c0, int c1, int zero_c0, int stage, isl_debug_conv_result* r) {
+  const uint32_t canary = b.a.esize == 4 ? DBG_CANARY32 : DBG_CANARY16;
+  const size_t body = b.a.frame_elems() * b.a.n, ce = b.a.chunk_elems(), fe = b.a.frame_elems();
+  const int Wp = b.a.W + 2 * b.a.pad;
+  for (size_t i = 0; i < b.elems(); ++i) {
+    const uint32_t v = b.bits(i);
+    int f = -1, chunk = i < b.slack ? -1 : 1, y = 0, x = (int)(i < b.slack ? i : i - b.slack - body), lane = 0;
+    bool inside = false, gap = false;
+    if (i >= b.slack && i < b.slack + body) {
+      const size_t rel = i - b.slack, rf = rel % fe, rc = rf % ce;
+      f = (int)(rel / fe); chunk = (int)(rf / ce); lane = (int)(rc % 8);
+      y = (int)(rc / 8 / Wp) - b.a.pad; x = (int)(rc / 8 % Wp) - b.a.pad;
+      const int ch = chunk * 8 + lane;
+      inside = y >= 0 && y < b.a.H && x >= 0 && x < b.a.W && ch >= c0 && ch < c1;
+      gap = inside && ch >= zero_c0;
+    }
+    if (inside && !gap) {
+      if (v == canary) ++r->unwritten;
+      continue;
+    }
+    if (gap ? v == 0 : v == canary) continue;
+    if (r->stray_writes++ == 0) {
+      r->stray_stage = stage; r->stray_frame = f; r->stray_chunk = chunk; r->stray_y = y; r->stray_x = x;
+      r->stray_lane = lane;
+    }
+  }
+}
+
+}  // namespace
+
+int isl_debug_conv(const isl_debug_conv_desc* dp, const float* x, const float* wgt, const float* bias,
+                   const float* slope, float* y, float* y_pool, isl_debug_conv_result* res) {
+  if (!dp || !x || !wgt || !bias || !y || !res) return fail(ISL_E_ARG, "isl_debug_conv: NULL argument");
+  const isl_debug_conv_desc d = *dp;
+  *res = isl_debug_conv_result{};
+  auto bad = [](const char* what) { return fail(ISL_E_ARG, std::string("isl_debug_conv: ") + what); };
+  for (int v : d.reserved) if (v) return bad("reserved field not zero");
+  if (d.n <= 0 || d.n > 256 || d.h <= 0 || d.w <= 0 || (long long)d.h * d.w > (1 << 20)) return bad("bad frame count or plane");
+  if (d.cin <= 0 || d.cin > 1024 || d.cout <= 0 || d.cout > 1024) return bad("bad channel count");
+  if (d.ks != 1 && d.ks != 3 && d.ks != 7) return bad("ks is 1, 3 or 7");
+  if (d.act != ACT_NONE && d.act != ACT_RELU && d.act != ACT_PRELU) return bad("act is 0, 1 or 2");
+  if (d.act == ACT_PRELU && !slope) return bad("PReLU without slopes");
+  if (d.kernel < ISL_DBG_X3 || d.kernel > ISL_DBG_RGB) return bad("unknown kernel");
+  const bool x3 = d.kernel == ISL_DBG_X3, rgb = d.kernel == ISL_DBG_RGB;
+  if ((d.f16 | d.act16 | d.allow_split | d.hpool | d.vin) & ~1) return bad("switches are 0 or 1");
+  if (d.act16 && !d.f16) return bad("act16 needs f16");
+  if (d.f16 && !x3 && !rgb) return bad("f16 is a form of the x3 and rgb kernels");
+  if ((d.hpool || d.vin || d.allow_split) && !x3) return bad("hpool, vin and allow_split are conv_x3's");
+  if ((d.in_pad != 1 && d.in_pad != 3) || (d.out_pad != 1 && d.out_pad != 3) || d.in_pad < d.ks / 2)
+    return bad("rings are 1 or 3 pixels, in_pad >= ks / 2");
+  if (d.nseg < 1 || d.nseg > 4) return bad("1 to 4 input segments");
+  // the channel map: the segments tile the logical channels, and do not overlap physically
+  int extent = 0;
+  std::vector<int> l2p(d.cin, -1);
+  for (int i = 0; i < d.nseg; ++i) {
+    const isl_debug_seg& sg = d.seg[i];
+    if (sg.len <= 0 || sg.phys < 0 || sg.logical < 0 || sg.logical + sg.len > d.cin || sg.phys + sg.len > 1024)
+      return bad("bad segment");
+    for (int k = 0; k < sg.len; ++k) {
+      if (l2p[sg.logical + k] >= 0) return bad("segments overlap");
+      l2p[sg.logical + k] = sg.phys + k;
+    }
+    extent = std::max(extent, sg.phys + sg.len);
+  }
+  const int cin_phys = round8(extent);
+  {
+    std::vector<char> used(cin_phys, 0);
+    for (int p : l2p) {
+      if (p < 0) return bad("a logical channel without a segment");
+      if (used[p]++) return bad("segments overlap");
+    }
+  }
+  if ((d.in_cs | d.in_coff | d.out_cs | d.out_coff) & 7 || d.in_coff < 0 || d.out_coff < 0 ||
+      d.in_coff + cin_phys > d.in_cs || d.out_coff + round8(d.cout) > d.out_cs || d.in_cs > 2048 || d.out_cs > 2048)
+    return bad("slices: multiples of 8 inside their buffers");
+  if (rgb && (d.cin != 3 || d.nseg != 1 || d.seg[0].phys != 0)) return bad("the rgb kernel takes 3 channels at the head of one chunk");
+  if (d.vin && (d.in_coff || d.in_cs != cin_phys)) return bad("vin reads a whole pair-max buffer");
+  if (d.hpool && (d.out_coff || (d.w & 1))) return bad("hpool writes a whole pair-max buffer of an even width");
+  if (d.hpool && !y_pool) return bad("hpool without y_pool");
+
+  ConvLayer c = mk("debug", d.cin, d.cout, d.ks, d.act);
+  c.w.assign(wgt, wgt + (size_t)d.cout * d.cin * d.ks * d.ks);
+  for (int i = 0; i < d.nseg; ++i) c.cmap.push_back({d.seg[i].logical, d.seg[i].phys, d.seg[i].len});
+  c.cin_phys = cin_phys;
+  c.bco = conv_bco_for(d.cout);
+  c.wbco = d.ks == 3 ? wino_bco_for(d.cout) : 0;
+  if (d.kernel == ISL_DBG_WINO && !c.wbco) return bad("shape not eligible for the fp32 Winograd kernel");
+
+  // buffers
+  const int esz_in = d.act16 && !rgb ? 2 : 4, esz_out = d.act16 ? 2 : 4;
+  DbgBuf in, out, pool;
+  if (d.vin) in.init(d.n, 2 * d.h, d.w, 0, d.in_cs, esz_in);
+  else in.init(d.n, d.h, d.w, d.in_pad, d.in_cs, esz_in);
+  if (d.hpool) out.init(d.n, d.h, d.w / 2, 0, d.out_cs, esz_out);
+  else out.init(d.n, d.h, d.w, d.out_pad, d.out_cs, esz_out);
+  if (d.hpool) pool.init(d.n, d.h / 2, d.w / 2, d.out_pad, d.out_cs, esz_out);
+  // (sizes first: the host images are allocated only once every buffer is within the limit)
+  if (in.bytes() > (256u << 20) || out.bytes() > (256u << 20) || (d.hpool && pool.bytes() > (256u << 20)))
+    return bad("buffer over 256 MiB");
+  in.alloc();
+  out.alloc();
+  if (d.hpool) pool.alloc();
+  in.fill(0, in.elems(), DBG_POISON32, DBG_POISON16);
+  for (int f = 0; f < d.n; ++f) {
+    for (int ch = 0; ch < cin_phys / 8; ++ch) in.fill(in.chunk_at(f, d.in_coff / 8 + ch), in.a.chunk_elems(), 0, 0);
+    for (int lc = 0; lc < d.cin; ++lc) {
+      const int pc = d.in_coff + l2p[lc];
+      if (d.vin) {
+        const float* xp = x + ((size_t)f * d.cin + lc) * 4 * d.h * d.w;
+        for (int yy = 0; yy < 2 * d.h; ++yy)
+          for (int xx = 0; xx < d.w; ++xx)
+            in.put(in.at(f, pc, yy, xx), std::max(xp[(size_t)yy * 2 * d.w + 2 * xx], xp[(size_t)yy * 2 * d.w + 2 * xx + 1]));
+      } else {
+        const float* xp = x + ((size_t)f * d.cin + lc) * d.h * d.w;
+        for (int yy = 0; yy < d.h; ++yy)
+          for (int xx = 0; xx < d.w; ++xx) in.put(in.at(f, pc, yy, xx), xp[(size_t)yy * d.w + xx]);
+      }
+    }
+  }
+  out.fill(0, out.elems(), DBG_CANARY32, DBG_CANARY16);
+  if (d.hpool) pool.fill(0, pool.elems(), DBG_CANARY32, DBG_CANARY16);
+
+  const size_t nb = ((size_t)d.cout + 255) / 256 * 256 + 256;   // bias / slopes padded to any channel tile
+  std::vector<float> hb(nb, 0.f), hs(nb, 0.f);
+  std::copy(bias, bias + d.cout, hb.begin());
+  if (d.act == ACT_PRELU) std::copy(slope, slope + d.cout, hs.begin());
+
+  ConvLaunch L;
+  L.in_pad = d.in_pad; L.in_cs = d.in_cs; L.in_coff = d.in_coff;
+  L.out_pad = d.hpool ? 0 : d.out_pad; L.out_cs = d.out_cs; L.out_coff = d.out_coff;
+  L.n = d.n; L.H = d.h; L.W = d.w; L.ks = d.ks; L.cin_chunks = cin_phys / 8;
+  L.cout = d.cout; L.bco = c.bco; L.act = d.act;
+  L.allow_split = d.allow_split;
+  L.vin = d.vin;
+  // the choices plan_steps makes for a launch, in its order; the shape checks need no device memory
+  std::vector<_Float16> pk16;
+  std::vector<float> pk32;
+  float inv = 1.f;
+  if (x3) {
+    if (!x3_fits(L)) return bad("shape does not fit conv_x3");
+    if (d.vin && !x3_vin_ok(L)) return bad("no pooled-input variant for this launch (x3_vin_ok)");
+    ConvLaunch Lw = L;
+    Lw.bco = 256;
+    if (x3_wide1_layer(d.ks, d.cout, cin_phys) && x3_wide1(Lw)) L.bco = 256;
+    L.f16 = d.f16;
+    if (d.act16) {
+      if (!x3_act16_ok(L)) return bad("no fp16-storage form of this launch (x3_act16_ok)");
+      L.act16 = 1;
+    }
+    if (d.hpool) {
+      if (!x3_hpool_ok(L)) return bad("no pair-max epilogue for this launch (x3_hpool_ok)");
+      L.hpool = 1;
+    }
+    pk16 = pack_x3(c, L.bco, &inv);
+    if (d.f16) pk16 = pack_hi_only(pk16, (size_t)2 * L.bco * 8);
+  } else if (rgb) {
+    L.f16 = d.f16; L.act16 = d.act16;
+    if (!rgb_layer(c) || !x3_rgb_fits(L)) return bad("shape does not fit the rgb kernel");
+    (void)pack_x3(c, c.bco, &inv);   // the same 2^s
+    pk16 = pack_x3_rgb(c);
+    if (d.f16) pk16 = pack_hi_only(pk16, (size_t)2 * 64 * 8);
+  } else if (d.kernel == ISL_DBG_WINO2) {
+    if (d.ks != 3 || d.cout % 64 || !wino_f16_fits(L)) return bad("shape not eligible for the Winograd kernel");
+    pk16 = pack_wino_f16(c, &inv);
+  } else if (d.kernel == ISL_DBG_WINO) {
+    L.bco = c.wbco;
+    pk32 = pack_wino(c);
+  } else {
+    pk32 = pack_weights(c);
+  }
+  L.wscale_inv = inv;
+
+  std::vector<void*> owned;
+  int flag = 0;
+  auto dmalloc = [&](void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
+    if (e == hipSuccess) owned.push_back(*p);
+    return e;
+  };
+  auto run = [&]() -> int {
+    float *d_b = nullptr, *d_s = nullptr, *d_ws = nullptr;
+    void* d_w = nullptr;
+    int* d_flag = nullptr;
+    const size_t wbytes = pk16.empty() ? pk32.size() * 4 : pk16.size() * sizeof(_Float16);
+    HIP_OK(dmalloc(&in.d, in.bytes()));
+    HIP_OK(dmalloc(&out.d, out.bytes()));
+    HIP_OK(dmalloc((void**)&d_b, nb * 4));
+    HIP_OK(dmalloc((void**)&d_s, nb * 4));
+    HIP_OK(dmalloc(&d_w, wbytes));
+    HIP_OK(dmalloc((void**)&d_flag, 4));
+    HIP_OK(hipMemcpy(in.d, in.h.data(), in.bytes(), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(out.d, out.h.data(), out.bytes(), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_b, hb.data(), nb * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_s, hs.data(), nb * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_w, pk16.empty() ? (const void*)pk32.data() : (const void*)pk16.data(), wbytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(d_flag, 0, 4));
+    L.in = (const float*)in.dev(); L.out = (float*)out.dev();
+    L.bias = d_b; L.slope = d_s; L.range_flag = d_flag;
+    if (pk16.empty()) L.wpk = (const float*)d_w; else L.wx3 = d_w;
+    if (x3) {
+      const size_t need = x3_splitk_ws_floats(L);
+      if (need > (64u << 20)) return bad("split-K workspace over 256 MiB");
+      if (need) {   // partial sums: a NaN where a reduce reads what no block wrote
+        std::vector<uint32_t> hw(need, DBG_POISON32);
+        HIP_OK(dmalloc((void**)&d_ws, need * 4));
+        HIP_OK(hipMemcpy(d_ws, hw.data(), need * 4, hipMemcpyHostToDevice));
+        L.ws = d_ws; L.ws_floats = need;
+      }
+      HIP_OK(launch_conv_x3(L, 0));
+      res->variant = x3_last_variant();
+    } else if (rgb) {
+      HIP_OK(launch_conv_x3_rgb(L, 0));
+      res->variant = x3_last_variant();
+    } else if (d.kernel == ISL_DBG_WINO2) {
+      HIP_OK(launch_wino_f16(L, 0));
+      res->variant = x3_variant_code(X3V_W2, 3, 128, 64);
+    } else if (d.kernel == ISL_DBG_WINO) {
+      HIP_OK(launch_wino(L, 0));
+    } else {
+      HIP_OK(launch_conv(L, 0));
+    }
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(out.h.data(), out.d, out.bytes(), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost));
+    if (d.hpool) {
+      // the arena's gap channels are zero (plan(): "zero rings and gap channels, once"); the pool
+      // copies whole chunks
+      std::vector<uint8_t> keep = out.h;
+      for (int f = 0; f < d.n; ++f)
+        for (int ch = d.cout; ch < round8(d.cout); ++ch)
+          for (int yy = 0; yy < out.a.H; ++yy)
+            for (int xx = 0; xx < out.a.W; ++xx) out.put(out.at(f, ch, yy, xx), 0.f);
+      HIP_OK(hipMemcpy(out.d, out.h.data(), out.bytes(), hipMemcpyHostToDevice));
+      out.h.swap(keep);
+      HIP_OK(dmalloc(&pool.d, pool.bytes()));
+      HIP_OK(hipMemcpy(pool.d, pool.h.data(), pool.bytes(), hipMemcpyHostToDevice));
+      Act ha = out.a, pa = pool.a;
+      ha.base = (float*)out.dev(); pa.base = (float*)pool.dev();
+      HIP_OK(launch_vpool2(ha, pa, d.cout, 0));
+      HIP_OK(hipDeviceSynchronize());
+      HIP_OK(hipMemcpy(pool.h.data(), pool.d, pool.bytes(), hipMemcpyDeviceToHost));
+    }
+    return ISL_OK;
+  };
+  const int rc = run();
+  for (void* p : owned) (void)hipFree(p);
+  if (rc) return rc;
+  res->range_flag = flag;
+  dbg_scan(out, d.out_coff, d.out_coff + d.cout, d.out_coff + d.cout, 0, res);
+  if (d.hpool) dbg_scan(pool, 0, round8(d.cout), d.cout, 1, res);
+  for (int f = 0; f < d.n; ++f)
+    for (int co = 0; co < d.cout; ++co) {
+      float* yp = y + ((size_t)f * d.cout + co) * out.a.H * out.a.W;
+      for (int yy = 0; yy < out.a.H; ++yy)
+        for (int xx = 0; xx < out.a.W; ++xx) yp[(size_t)yy * out.a.W + xx] = out.get(out.at(f, d.out_coff + co, yy, xx));
+      if (!d.hpool) continue;
+      float* pp = y_pool + ((size_t)f * d.cout + co) * pool.a.H * pool.a.W;
+      for (int yy = 0; yy < pool.a.H; ++yy)
+        for (int xx = 0; xx < pool.a.W; ++xx) pp[(size_t)yy * pool.a.W + xx] = pool.get(pool.at(f, co, yy, xx));
+    }
+  if (flag && d.range_error) return fail(ISL_E_RANGE, "isl_debug_conv: the layer left the fp16 split range");
+  return ISL_OK;
+}
+
 int isl_debug_conv3x3(const float* x, int n, int cin, int h, int w, const float* wgt, const float* bias,
                       const float* slope, int cout, int kernel, float* y) {
   if (!x || !wgt || !bias || !slope || !y) return fail(ISL_E_ARG, "isl_debug_conv3x3: NULL argument");
   if (n <= 0 || n > 64 || cin <= 0 || cin > 1024 || cin % 8 || cout <= 0 || cout > 1024 || h <= 0 || w <= 0 ||
       (long long)h * w > (1 << 20) || (kernel != 0 && kernel != 1))
     return fail(ISL_E_ARG, "isl_debug_conv3x3: bad argument");
-  ConvLayer c = mk("debug", cin, cout, 3, ACT_PRELU);
-  c.w.assign(wgt, wgt + (size_t)cout * cin * 9);
-  c.cmap = {{0, 0, cin}};
-  c.cin_phys = cin;
-  c.bco = conv_bco_for(cout);
-  Act in, out;
-  in.n = out.n = n; in.H = out.H = h; in.W = out.W = w; in.pad = out.pad = 1;
-  in.cs = cin; out.cs = round8(cout);
-  // the activations' layout: [n][chunk of 8 channels][h + 2][w + 2][8], a zero ring
-  const int Wp = w + 2;
-  std::vector<float> hin(in.frame_elems() * n, 0.f), hout(out.frame_elems() * n);
-  for (int f = 0; f < n; ++f)
-    for (int ch = 0; ch < cin; ++ch)
-      for (int yy = 0; yy < h; ++yy)
-        for (int xx = 0; xx < w; ++xx)
-          hin[((size_t)f * (cin / 8) + ch / 8) * in.chunk_elems() + ((size_t)(yy + 1) * Wp + xx + 1) * 8 + ch % 8] =
-              x[(((size_t)f * cin + ch) * h + yy) * w + xx];
-  const size_t nb = ((size_t)cout + 255) / 256 * 256 + 256;   // bias / slopes padded to any channel tile
-  std::vector<float> hb(nb, 0.f), hs(nb, 0.f);
-  std::copy(bias, bias + cout, hb.begin());
-  std::copy(slope, slope + cout, hs.begin());
-  float inv = 1.f;
-  const std::vector<_Float16> pk = kernel == 1 && cout % 64 == 0 ? pack_wino_f16(c, &inv) : pack_x3(c, c.bco, &inv);
-  float *d_in = nullptr, *d_out = nullptr, *d_b = nullptr, *d_s = nullptr;
-  void* d_w = nullptr;
-  int* d_flag = nullptr;
-  int flag = 0;
-  auto run = [&]() -> int {
-    HIP_OK(hipMalloc(&d_in, in.bytes()));
-    HIP_OK(hipMalloc(&d_out, out.bytes()));
-    HIP_OK(hipMalloc(&d_b, nb * 4));
-    HIP_OK(hipMalloc(&d_s, nb * 4));
-    HIP_OK(hipMalloc(&d_w, pk.size() * sizeof(_Float16)));
-    HIP_OK(hipMalloc(&d_flag, 4));
-    HIP_OK(hipMemcpy(d_in, hin.data(), in.bytes(), hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(d_out, 0, out.bytes()));
-    HIP_OK(hipMemcpy(d_b, hb.data(), nb * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_s, hs.data(), nb * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_w, pk.data(), pk.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(d_flag, 0, 4));
-    ConvLaunch L;
-    L.in = d_in; L.in_pad = 1; L.in_cs = in.cs; L.in_coff = 0;
-    L.out = d_out; L.out_pad = 1; L.out_cs = out.cs; L.out_coff = 0;
-    L.wpk = nullptr; L.bias = d_b; L.slope = d_s;
-    L.n = n; L.H = h; L.W = w; L.ks = 3; L.cin_chunks = cin / 8;
-    L.cout = cout; L.bco = c.bco; L.act = ACT_PRELU;
-    L.wx3 = d_w; L.wscale_inv = inv; L.range_flag = d_flag;
-    if (kernel == 1) {
-      if (!wino_f16_fits(L)) return fail(ISL_E_ARG, "isl_debug_conv3x3: shape not eligible for the Winograd kernel");
-      HIP_OK(launch_wino_f16(L, 0));
-    } else {
-      if (!x3_fits(L)) return fail(ISL_E_ARG, "isl_debug_conv3x3: shape does not fit conv_x3");
-      HIP_OK(launch_conv_x3(L, 0));
-    }
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(hout.data(), d_out, out.bytes(), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost));
-    return ISL_OK;
-  };
-  const int rc = run();
-  for (void* p : {(void*)d_in, (void*)d_out, (void*)d_b, (void*)d_s, d_w, (void*)d_flag})
-    if (p) (void)hipFree(p);
-  if (rc) return rc;
-  if (flag) return fail(ISL_E_RANGE, "isl_debug_conv3x3: the layer left the fp16 split range");
-  const int Co8 = out.cs / 8;
-  for (int f = 0; f < n; ++f)
-    for (int co = 0; co < cout; ++co)
-      for (int yy = 0; yy < h; ++yy)
-        for (int xx = 0; xx < w; ++xx)
-          y[(((size_t)f * cout + co) * h + yy) * w + xx] =
-              hout[((size_t)f * Co8 + co / 8) * out.chunk_elems() + ((size_t)(yy + 1) * Wp + xx + 1) * 8 + co % 8];
-  return ISL_OK;
+  isl_debug_conv_desc d{};
+  d.n = n; d.h = h; d.w = w; d.cin = cin; d.cout = cout; d.ks = 3; d.act = ACT_PRELU;
+  d.kernel = kernel == 1 ? ISL_DBG_WINO2 : ISL_DBG_X3;
+  d.in_pad = d.out_pad = 1;
+  d.in_cs = cin; d.out_cs = round8(cout);
+  d.nseg = 1;
+  d.seg[0] = {0, 0, cin};
+  d.range_error = 1;
+  isl_debug_conv_result r;
+  return isl_debug_conv(&d, x, wgt, bias, slope, y, nullptr, &r);
 }
 
 }  // extern "C"

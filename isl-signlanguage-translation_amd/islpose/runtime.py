@@ -126,7 +126,7 @@ EXPORTS = ["isl_abi_version", "isl_last_error", "isl_net_create", "isl_net_destr
            "isl_net_get_act_storage", "isl_net_act_storage_active", "isl_post_opts_default",
            "isl_body_post_opts", "isl_hand_post_opts", "isl_hand_post_crops_opts",
            "isl_net_preprocess_crops_flip", "isl_hand_post_ex", "isl_hand_post_crops_ex", "isl_augment",
-           "isl_debug_conv3x3"]
+           "isl_debug_conv3x3", "isl_debug_conv"]
 
 
 class IslCaps(ctypes.Structure):
@@ -159,6 +159,105 @@ class IslAugItem(ctypes.Structure):
     _fields_ = [("c", ctypes.c_double), ("s", ctypes.c_double), ("src", ctypes.c_int32),
                 ("rotate", ctypes.c_int32), ("threshold", ctypes.c_int32), ("swap_rb", ctypes.c_int32),
                 ("reserved", ctypes.c_int32 * 2)]
+
+
+class IslDebugSeg(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("phys", "logical", "len")]
+
+
+class IslDebugConvDesc(ctypes.Structure):
+    """isl_debug_conv_desc (include/islpose.h)."""
+    _fields_ = ([(n, ctypes.c_int32) for n in
+                 ("n", "h", "w", "cin", "cout", "ks", "act", "kernel", "f16", "act16", "allow_split",
+                  "in_pad", "out_pad", "in_cs", "in_coff", "out_cs", "out_coff", "nseg")] +
+                [("seg", IslDebugSeg * 4), ("hpool", ctypes.c_int32), ("vin", ctypes.c_int32),
+                 ("range_error", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)])
+
+
+class IslDebugConvResult(ctypes.Structure):
+    """isl_debug_conv_result (include/islpose.h)."""
+    _fields_ = [("variant", ctypes.c_int32), ("range_flag", ctypes.c_int32),
+                ("stray_writes", ctypes.c_int64), ("unwritten", ctypes.c_int64),
+                ("stray_stage", ctypes.c_int32), ("stray_frame", ctypes.c_int32),
+                ("stray_chunk", ctypes.c_int32), ("stray_y", ctypes.c_int32), ("stray_x", ctypes.c_int32),
+                ("stray_lane", ctypes.c_int32), ("reserved", ctypes.c_int32 * 6)]
+
+
+DEBUG_KERNELS = {"x3": 0, "wino2": 1, "direct": 2, "wino": 3, "rgb": 4}
+DEBUG_ACTS = {"none": 0, "relu": 1, "prelu": 2}
+
+
+class DebugConvResult:
+    """What isl_debug_conv returns: y (numpy fp32 [n, cout, h, w]; with hpool the pair-max map
+    [n, cout, h, w // 2]), pooled (with hpool: [n, cout, h // 2, w // 2], else None), variant (the
+    x3 variant code; decode_variant reads it), range_flag, stray_writes and unwritten (element
+    counts), stray (the first stray write as a dict, or None)."""
+
+    def __init__(self, y, pooled, r):
+        self.y, self.pooled = y, pooled
+        self.variant, self.range_flag = int(r.variant), int(r.range_flag)
+        self.stray_writes, self.unwritten = int(r.stray_writes), int(r.unwritten)
+        self.stray = None if not self.stray_writes else dict(
+            stage="pool" if r.stray_stage else "conv", frame=int(r.stray_frame), chunk=int(r.stray_chunk),
+            y=int(r.stray_y), x=int(r.stray_x), lane=int(r.stray_lane))
+
+
+def debug_conv(x, weight, bias, slope=None, *, act="none", kernel="x3", f16=False, act16=False,
+               allow_split=False, in_pad=None, out_pad=1, in_cs=None, in_coff=0, out_cs=None, out_coff=0,
+               segs=None, hpool=False, vin=False, range_error=False):
+    """One convolution layer on one of the conv kernels, on host arrays (isl_debug_conv; the
+    header describes the buffers, the canary and the poison).  x [n, cin, h, w] (with vin the
+    pre-pool map [n, cin, 2h, 2w]), weight [cout, cin, ks, ks], bias [cout], slope [cout] for
+    act "prelu".  segs: up to four (phys, logical, len) triples, default one segment of all
+    channels; in_cs / out_cs default to the smallest buffers that hold the slices; in_pad
+    defaults to max(1, ks // 2).  Returns a DebugConvResult."""
+    import numpy as np
+    x, weight, bias = (np.ascontiguousarray(a, np.float32) for a in (x, weight, bias))
+    if x.ndim != 4 or weight.ndim != 4 or weight.shape[2] != weight.shape[3] or weight.shape[1] != x.shape[1]:
+        raise ValueError("debug_conv: x [n, cin, h, w] and weight [cout, cin, ks, ks] expected")
+    n, cin, h, w = x.shape
+    cout, ks = weight.shape[0], weight.shape[2]
+    if vin:
+        if h % 2 or w % 2:
+            raise ValueError("debug_conv: vin takes an even pre-pool map")
+        h, w = h // 2, w // 2
+    if bias.shape != (cout,):
+        raise ValueError("debug_conv: bias [cout] expected")
+    if kernel not in DEBUG_KERNELS or act not in DEBUG_ACTS:
+        raise ValueError("debug_conv: kernel is one of %s, act one of %s" % (sorted(DEBUG_KERNELS), sorted(DEBUG_ACTS)))
+    if act == "prelu":
+        if slope is None:
+            raise ValueError("debug_conv: act 'prelu' needs slopes")
+        slope = np.ascontiguousarray(slope, np.float32)
+        if slope.shape != (cout,):
+            raise ValueError("debug_conv: slope [cout] expected")
+    else:
+        slope = None
+    segs = [(0, 0, cin)] if segs is None else [tuple(int(v) for v in s) for s in segs]
+    if not 1 <= len(segs) <= 4:
+        raise ValueError("debug_conv: 1 to 4 segments")
+    phys = (max(p + l for p, _, l in segs) + 7) // 8 * 8
+    d = IslDebugConvDesc()
+    d.n, d.h, d.w, d.cin, d.cout, d.ks = n, h, w, cin, cout, ks
+    d.act, d.kernel = DEBUG_ACTS[act], DEBUG_KERNELS[kernel]
+    d.f16, d.act16, d.allow_split = int(bool(f16)), int(bool(act16)), int(bool(allow_split))
+    d.in_pad = max(1, ks // 2) if in_pad is None else int(in_pad)
+    d.out_pad = int(out_pad)
+    d.in_coff, d.out_coff = int(in_coff), int(out_coff)
+    d.in_cs = d.in_coff + phys if in_cs is None else int(in_cs)
+    d.out_cs = d.out_coff + (cout + 7) // 8 * 8 if out_cs is None else int(out_cs)
+    d.nseg = len(segs)
+    for i, (p, lg, ln) in enumerate(segs):
+        d.seg[i] = IslDebugSeg(p, lg, ln)
+    d.hpool, d.vin, d.range_error = int(bool(hpool)), int(bool(vin)), int(bool(range_error))
+    y = np.empty((n, cout, h, w // 2 if hpool else w), np.float32)
+    pooled = np.empty((n, cout, h // 2, w // 2), np.float32) if hpool else None
+    r = IslDebugConvResult()
+    check(lib().isl_debug_conv(ctypes.byref(d), x.ctypes.data, weight.ctypes.data, bias.ctypes.data,
+                               None if slope is None else slope.ctypes.data, y.ctypes.data,
+                               None if pooled is None else pooled.ctypes.data, ctypes.byref(r)),
+          "isl_debug_conv")
+    return DebugConvResult(y, pooled, r)
 
 
 def post_opts_struct(opts: dict) -> IslPostOpts:
@@ -236,6 +335,8 @@ def lib():
     L.isl_hand_post_crops_ex.argtypes = L.isl_hand_post_crops_opts.argtypes + [pu8, vp]
     L.isl_augment.argtypes = [vp, i32, i32, i32, vp, ctypes.POINTER(IslAugItem), i32, vp]
     L.isl_debug_conv3x3.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]
+    L.isl_debug_conv.argtypes = [ctypes.POINTER(IslDebugConvDesc), vp, vp, vp, vp, vp, vp,
+                                 ctypes.POINTER(IslDebugConvResult)]
     for name in EXPORTS[2:]:
         getattr(L, name).restype = i32
     if L.isl_abi_version() != 1:

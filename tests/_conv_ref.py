@@ -1,0 +1,468 @@
+"""Float64 references, per-element error bounds and numpy emulations of the conv kernels, for
+tests/test_conv_ref.py (CPU) and tests/test_gpu_conv_layers.py (one layer through
+rt.debug_conv on an MI355X).
+
+Notation.  u = 2^-24 is the fp32 unit round-off, gamma(n) = n u / (1 - n u) the bound of n
+accumulated roundings (Higham, Accuracy and Stability of Numerical Algorithms, Lemma 3.1).
+K = cin * ks^2 is the number of products of one output.  Per output element, all in float64:
+
+  A  = sum |x| |w| + |b|                absum(): the convolution of the absolute values
+  B  = sum |w| over the taps inside the image                                   wsum()
+  X1 = sum |x| over those taps                                                  xsum()
+
+Summation.  A sum of n fp32 terms taken in ANY order (a chain, a tree, the canonical K ranges,
+split-K partial sums added by x3_splitk_reduce) passes every term through at most n - 1 rounded
+additions, so its error is at most gamma(n - 1) sum |terms|.  The matrix cores' internal order
+is not documented; the bound does not need it.
+
+Three-term conv_x3 (csrc/conv_x3.hip lines 1-22, pack_x3 in csrc/runtime.cpp).
+  x = xh + xl + rx with xh = fp16(x), xl = fp16(x - xh) (the subtraction is exact in fp32).
+  fp16 carries 11 bits: |x - xh| <= 2^-11 |x| while xh is a normal number, and
+  |rx| <= 2^-11 |x - xh| <= 2^-22 |x| while xl is one.  An fp16 subnormal is a multiple of 2^-24,
+  so below the normal range a rounding errs by at most 2^-25 absolutely -- the "absolute error
+  <= 2^-25" of line 18.  In every case |rx| <= 2^-22 |x| + 2^-25.
+  w' = w 2^s (exact; max |w'| in [2^13, 2^14)) = wh + wl + rw in the same way:
+  |rw| <= 2^-22 |w'| + 2^-25, i.e. 2^-22 |w| + 2^-25 2^-s after the epilogue's exact 2^-s.
+  The kernel sums xh wh + xh wl + xl wh (each product exact in fp32: 11 x 11 bits).  Against
+  x w' that misses  xl wl + rx w' + (xh + xl) rw, at most
+      3 * 2^-22 |x| |w'| + 2^-25 |w'| + 2^-25 |x|,
+  times 1 + 2^-10 for the second-order terms (|xl| <= 2^-11 |x| (1 + 2^-11), ...).  Hence
+      c_s = 1.5 (1 + 2^-10)        on 2^-21 A     (the dropped lo*lo term and both residuals)
+      c_u = 1 + 2^-10              on 2^-25 B'    B' = B + 2^-s X1: the subnormal lo halves of
+                                                   the activations (B) and of the filters (X1)
+  The 3K products, the bias and the activation's multiply make 3K - 1 + 2 roundings of terms
+  whose absolute sum is at most (1 + 2^-9) A (|xh| <= (1 + 2^-11) |x|, |wl| <= 2^-11 |w'|):
+      c_K = 3, c_0 = 2:   gamma(3K + 2) (1 + 2^-9) A
+  bound_x3 = act * [gamma(3K + 2)(1 + 2^-9) A + c_s 2^-21 A + c_u 2^-25 B'].
+  act = max(1, |slope|) for PReLU, 1 otherwise: where y and ref have one sign the activation
+  scales the error by 1 or |slope|; where they differ |ref| <= |y - ref| and the same factor holds.
+
+conv_x3_rgb is the same arithmetic with K = 27.
+
+One-term (ISL_PREC_FP16, include/islpose.h): the operands are rounded once, x to fp16(x) and w to
+fp16(w 2^s) 2^-s, the products are exact in fp32, the accumulation is fp32.  Against ref64 of the
+ROUNDED operands only the summation remains:  bound_f16 = act * gamma(K + 2) A(rounded operands).
+
+direct (csrc/conv.hip, fp32 matrix cores): fp32 operands are exact; K products and K - 1 + 2
+additions round:  bound_direct = act * gamma(2K + 2) A.
+
+wino (csrc/wino.hip, F(2x2, 3x3) in fp32): U = G g G^T in float64 rounded once to fp32, V = B^T d B
+in fp32 (two additions per entry), M = sum_ci U V (cin products, cin - 1 additions), Y = A^T M A
+(four additions), bias, activation: 2 cin + 9 roundings.  The cancellation in B^T d B makes A the
+wrong yardstick; the Winograd-domain absolute sum is
+      A_wino  = |A^T| (sum_ci |U| . |V|) |A| + |b|,       V = B^T d B in float64,
+and the two roundings of V act on |B^T| |d| |B| >= |V|, which needs the companion
+      A_wino2 = |A^T| (sum_ci |U| . (|B^T| |d| |B|)) |A|:
+  bound_wino = act * [gamma(2 cin + 7) A_wino + gamma(2) (1 + 2^-10) A_wino2].
+
+wino2 (csrc/wino_f16.hip): the same transforms with the three-term split of U 2^s and V:
+  bound_wino2 = act * [gamma(3 cin + 7)(1 + 2^-9) A_wino + c_s 2^-21 A_wino
+                       + gamma(2)(1 + 2^-10) A_wino2 + c_u 2^-25 (B_wino + 2^-s X_wino)],
+  B_wino = |A^T| (sum_ci |U|) |A|, X_wino = |A^T| (sum_ci |V|) |A|.
+
+fp16 storage (ISL_ACT_FP16): the epilogue stores RNE(v) of a value v within the bound E of ref:
+  |y - ref| <= E + half an fp16 ulp at |ref| + E   (bound_act16).
+
+Headroom (test_conv_ref.py::test_headroom_of_native_fp32, uniform(-1, 1) inputs): a plain native
+fp32 convolution (torch CPU, float32) has max |y - ref| / bound_x3 of 0.042 (1x1, 16 channels: 1/24),
+0.0025 (3x3, 24 channels: 1/397) and 0.0008 (3x3, 64 channels: 1/1250); against bound_direct 0.078,
+0.0039 and 0.0012.  The worst-case bound grows with K, the roundings' random walk with sqrt(K).  On
+the MI355X the three-term kernels sit at 0.0001 .. 0.09 of bound_x3 (the same ratios as native fp32),
+the one-term kernels at 0.0003 .. 0.17 of bound_f16, and the fp16-storage forms at 0.47 .. 0.999 of
+bound_act16, which the half ulp of the stored rounding leads: a truncation instead of the rounding
+to nearest, or a double rounding, would break it.  On small magnitudes (1e-5 .. 1e-3, K = 16) the
+emulation reaches 0.62 of the bound and 59.6 times the bound without its 2^-25 B' term.
+
+The bound is not vacuous for being loose in the sum: it is per element and normalised by A there,
+where the whole-net bar max |d| / max |ref| < 1e-4 is one number per tensor.  The mutation checks of
+test_conv_ref.py (a dropped corner tap, a skipped chunk pair of one channel, two channels swapped,
+a tile-tail pixel from the next row, a missing bias, a neighbour's PReLU slope) break the
+elementwise bound by factors of 55 to 370000 at every shape tried.  Put on the same one-layer
+output the old bar sees all six as well (0.012 .. 1.5 against 1e-4: on one layer's own output they
+are gross); what it cannot see is the same mistake in a quiet part of the tensor.  With a loud
+frame (x 3000) beside the mutated quiet one, five of the six stay under 1e-4 of the tensor's maximum
+(1.5e-5 .. 7.9e-5; the missing bias 7e-9) while the elementwise ratio is 1.56 .. 10600; only the
+neighbour's slope still shows (1.2e-4).  Ten more layers and a max over the map dilute further.
+"""
+import numpy as np
+import torch
+
+U32 = 2.0 ** -24
+C_S = 1.5 * (1 + 2.0 ** -10)
+C_U = 1 + 2.0 ** -10
+F16_MAX = 65504.0
+
+ACTS = ("none", "relu", "prelu")
+
+
+def gamma(n):
+    return n * U32 / (1.0 - n * U32)
+
+
+# ---- references -----------------------------------------------------------------------------
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a, np.float64))
+
+
+def activate(t, slope, act):
+    """The activation of a float64 tensor [n, cout, h, w] (numpy in, numpy out)."""
+    if act == "relu":
+        return np.maximum(t, 0.0)
+    if act == "prelu":
+        return np.where(t >= 0, t, t * np.asarray(slope, np.float64)[None, :, None, None])
+    return t
+
+
+def conv64(x, w, b):
+    ks = w.shape[2]
+    return torch.nn.functional.conv2d(_t(x), _t(w), None if b is None else _t(b), padding=ks // 2).numpy()
+
+
+def ref64(x, w, b, slope=None, ks=None, act="none"):
+    """torch-CPU conv2d in float64 (stride 1, 'same' padding), bias, activation."""
+    assert ks is None or ks == w.shape[2]
+    return activate(conv64(x, w, b), slope, act)
+
+
+def hpool(y):
+    """Max of horizontal pixel pairs (even width): the pair-max map of ConvLaunch::hpool."""
+    return np.maximum(y[..., 0::2], y[..., 1::2])
+
+
+def pool2(y):
+    """MaxPool2d(2, 2), floor mode."""
+    h, w = y.shape[2] // 2 * 2, y.shape[3] // 2 * 2
+    y = y[:, :, :h, :w]
+    return np.maximum(np.maximum(y[:, :, 0::2, 0::2], y[:, :, 0::2, 1::2]),
+                      np.maximum(y[:, :, 1::2, 0::2], y[:, :, 1::2, 1::2]))
+
+
+def absum(x, w, b):
+    """A: the same convolution of |x|, |w|, |b| in float64."""
+    return conv64(np.abs(x), np.abs(w), np.abs(b))
+
+
+def wsum(w, h, wd):
+    """B: per element, sum |w| over the taps that fall inside the image; [1, cout, h, w]."""
+    return conv64(np.ones((1, w.shape[1], h, wd)), np.abs(w), None)
+
+
+def xsum(x, ks):
+    """X1: per pixel, sum |x| over the window's taps inside the image; [n, 1, h, w]."""
+    return conv64(np.abs(x), np.ones((1, x.shape[1], ks, ks)), None)
+
+
+# ---- operand roundings ----------------------------------------------------------------------
+
+def pack_exp(w):
+    """pack_x3's s: max |w| 2^s in [2^13, 2^14) (0 for an all-zero filter)."""
+    mx = float(np.max(np.abs(np.asarray(w, np.float32)))) if np.size(w) else 0.0
+    if mx == 0.0:
+        return 0
+    _, e = np.frexp(np.float32(mx))
+    return 14 - int(e)
+
+
+def f16(a):
+    """Round to nearest even to fp16, returned as float32."""
+    return np.asarray(a, np.float32).astype(np.float16).astype(np.float32)
+
+
+def round_w_f16(w, s=None):
+    """The one-term filters: fp16(w 2^s) 2^-s."""
+    s = pack_exp(w) if s is None else s
+    return np.ldexp(f16(np.ldexp(np.asarray(w, np.float32), s)), -s).astype(np.float32)
+
+
+def half_ulp16(m):
+    """Half an fp16 ulp at magnitude m (2^-25 below the normal range)."""
+    m = np.maximum(np.asarray(m, np.float64), 2.0 ** -14)
+    return np.ldexp(1.0, np.floor(np.log2(m)).astype(np.int64) - 11)
+
+
+# ---- bounds ---------------------------------------------------------------------------------
+
+def act_factor(slope, act):
+    if act == "prelu":
+        return np.maximum(1.0, np.abs(np.asarray(slope, np.float64)))[None, :, None, None]
+    return 1.0
+
+
+def bound_x3(x, w, b, slope=None, act="none", abs_term=True):
+    """Three-term conv_x3 / conv_x3_rgb against ref64(x, w, b).  abs_term=False drops the
+    2^-25 B' term (the small-magnitude test shows it is needed)."""
+    K = w.shape[1] * w.shape[2] * w.shape[3]
+    A = absum(x, w, b)
+    e = gamma(3 * K + 2) * (1 + 2.0 ** -9) * A + C_S * 2.0 ** -21 * A
+    if abs_term:
+        Bp = wsum(w, x.shape[2], x.shape[3]) + np.ldexp(1.0, -pack_exp(w)) * xsum(x, w.shape[2])
+        e = e + C_U * 2.0 ** -25 * Bp
+    return act_factor(slope, act) * e
+
+
+def bound_f16(xr, wr, b, slope=None, act="none"):
+    """One-term kernels against ref64 of the rounded operands xr = f16(x), wr = round_w_f16(w)."""
+    K = wr.shape[1] * wr.shape[2] * wr.shape[3]
+    return act_factor(slope, act) * gamma(K + 2) * absum(xr, wr, b)
+
+
+def bound_direct(x, w, b, slope=None, act="none"):
+    K = w.shape[1] * w.shape[2] * w.shape[3]
+    return act_factor(slope, act) * gamma(2 * K + 2) * absum(x, w, b)
+
+
+def bound_act16(bound, ref):
+    return bound + half_ulp16(np.abs(ref) + bound)
+
+
+# Winograd F(2x2, 3x3)
+_G = np.array([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], np.float64)
+_BT = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], np.float64)
+_AT = np.array([[1, 1, 1, 0], [0, 1, -1, -1]], np.float64)
+
+
+def _tiles(x, dtype=np.float64):
+    """The 4x4 input tiles d [n, cin, th, tw, 4, 4] of the zero-padded map (pad 1, odd sizes
+    padded to whole tiles)."""
+    n, c, h, w = x.shape
+    th, tw = (h + 1) // 2, (w + 1) // 2
+    xp = np.zeros((n, c, 2 * th + 2, 2 * tw + 2), dtype)
+    xp[:, :, 1:h + 1, 1:w + 1] = x
+    d = np.empty((n, c, th, tw, 4, 4), dtype)
+    for i in range(4):
+        for j in range(4):
+            d[..., i, j] = xp[:, :, i:i + 2 * th:2, j:j + 2 * tw:2]
+    return d
+
+
+def _untile(y, h, w):
+    """[n, cout, th, tw, 2, 2] -> [n, cout, h, w]."""
+    n, c, th, tw = y.shape[:4]
+    return y.transpose(0, 1, 2, 4, 3, 5).reshape(n, c, 2 * th, 2 * tw)[:, :, :h, :w]
+
+
+def wino_sums(x, w, b):
+    """(A_wino, A_wino2, B_wino, X_wino, s) of the module docstring, each [n, cout, h, w]
+    (B_wino: [1, ...]); s = pack_wino_f16's exponent (max |U| 2^s in [2^13, 2^14))."""
+    h, wd = x.shape[2], x.shape[3]
+    U = np.einsum("ik,ockl,jl->ocij", _G, np.asarray(w, np.float64), _G)
+    d = _tiles(np.asarray(x, np.float64))
+    V = np.einsum("ik,ncabkl,jl->ncabij", _BT, d, _BT)
+    V2 = np.einsum("ik,ncabkl,jl->ncabij", np.abs(_BT), np.abs(d), np.abs(_BT))
+    aA = np.abs(_AT)
+
+    def back(M):
+        return _untile(np.einsum("ik,noabkl,jl->noabij", aA, M, aA), h, wd)
+    aU = np.abs(U)
+    Aw = back(np.einsum("ocij,ncabij->noabij", aU, np.abs(V))) + np.abs(np.asarray(b, np.float64))[None, :, None, None]
+    Aw2 = back(np.einsum("ocij,ncabij->noabij", aU, V2))
+    ones = np.ones((1,) + V.shape[1:])
+    Bw = back(np.einsum("ocij,ncabij->noabij", aU, ones))
+    Xw = back(np.einsum("ocij,ncabij->noabij", np.ones_like(aU), np.abs(V)))
+    mx = float(np.max(np.abs(U)))
+    s = 0 if mx == 0.0 else 14 - int(np.frexp(mx)[1])
+    return Aw, Aw2, Bw, Xw, s
+
+
+def bound_wino(x, w, b, slope=None, act="none"):
+    cin = w.shape[1]
+    Aw, Aw2, _, _, _ = wino_sums(x, w, b)
+    return act_factor(slope, act) * (gamma(2 * cin + 7) * Aw + gamma(2) * (1 + 2.0 ** -10) * Aw2)
+
+
+def bound_wino2(x, w, b, slope=None, act="none"):
+    cin = w.shape[1]
+    Aw, Aw2, Bw, Xw, s = wino_sums(x, w, b)
+    e = (gamma(3 * cin + 7) * (1 + 2.0 ** -9) * Aw + C_S * 2.0 ** -21 * Aw + gamma(2) * (1 + 2.0 ** -10) * Aw2 +
+         C_U * 2.0 ** -25 * (Bw + np.ldexp(1.0, -s) * Xw))
+    return act_factor(slope, act) * e
+
+
+# ---- emulations (the reference arithmetic alone must pass its own bound) --------------------
+
+def _im2col(x, ks):
+    """[n, cin, h, w] -> [cin * ks * ks, n * h * w] float32, k = (ci, ky, kx) as OIHW filters."""
+    x = np.asarray(x, np.float32)
+    n, c, h, w = x.shape
+    p = ks // 2
+    xp = np.zeros((n, c, h + 2 * p, w + 2 * p), np.float32)
+    xp[:, :, p:p + h, p:p + w] = x
+    cols = np.empty((c, ks, ks, n, h, w), np.float32)
+    for ky in range(ks):
+        for kx in range(ks):
+            cols[:, ky, kx] = xp[:, :, ky:ky + h, kx:kx + w].transpose(1, 0, 2, 3)
+    return cols.reshape(c * ks * ks, n * h * w)
+
+
+def _epilogue(acc, scale_inv, b, slope, act, shape):
+    n, cout, h, w = shape
+    v = (acc * np.float32(scale_inv) + np.asarray(b, np.float32)[:, None]).astype(np.float32)
+    v = v.reshape(cout, n, h, w).transpose(1, 0, 2, 3)
+    if act == "relu":
+        v = np.maximum(v, np.float32(0))
+    elif act == "prelu":
+        v = np.where(v >= 0, v, v * np.asarray(slope, np.float32)[None, :, None, None]).astype(np.float32)
+    return np.ascontiguousarray(v, np.float32)
+
+
+def emu_x3(x, w, b, slope=None, act="none", seed=0, terms=3):
+    """The split arithmetic in numpy: fp16 hi / lo of x, fp16 hi / lo of w 2^s, the three exact
+    products of every (tap, channel) added one by one into a float32 accumulator in a shuffled
+    order, the epilogue's 2^-s, bias and activation in float32.  terms=1: the one-term mode."""
+    x, w = np.asarray(x, np.float32), np.asarray(w, np.float32)
+    n, cin, h, wd = x.shape
+    cout, ks = w.shape[0], w.shape[2]
+    s = pack_exp(w)
+    ws = np.ldexp(w, s).astype(np.float32).reshape(cout, -1)
+    wh = f16(ws)
+    wl = f16(ws - wh)
+    X = _im2col(x, ks)
+    xh = f16(X)
+    xl = f16(X - xh)
+    ops = [(wh, xh)] if terms == 1 else [(wh, xh), (wl, xh), (wh, xl)]
+    order = [(k, t) for k in range(X.shape[0]) for t in range(len(ops))]
+    np.random.default_rng(seed).shuffle(order)
+    acc = np.zeros((cout, X.shape[1]), np.float32)
+    for k, t in order:
+        a, v = ops[t]
+        acc += a[:, k, None] * v[None, k, :]      # the product is exact in fp32, the += rounds
+    return _epilogue(acc, np.ldexp(1.0, -s), b, slope, act, (n, cout, h, wd))
+
+
+def emu_wino32(x, w, b, slope=None, act="none"):
+    """F(2x2, 3x3) restated in float32: U from float64 rounded once, V, M and Y in float32."""
+    x = np.asarray(x, np.float32)
+    n, cin, h, wd = x.shape
+    cout = w.shape[0]
+    U = np.einsum("ik,ockl,jl->ocij", _G, np.asarray(w, np.float64), _G).astype(np.float32)
+    d = _tiles(x, np.float32)
+    bt = _BT.astype(np.float32)
+    t = np.zeros(d.shape, np.float32)
+    for i in range(4):                                   # rows of B^T have two nonzeros
+        (r0, r1) = np.nonzero(bt[i])[0]
+        t[..., i, :] = bt[i, r0] * d[..., r0, :] + bt[i, r1] * d[..., r1, :]
+    V = np.zeros(d.shape, np.float32)
+    for j in range(4):
+        (r0, r1) = np.nonzero(bt[j])[0]
+        V[..., j] = bt[j, r0] * t[..., r0] + bt[j, r1] * t[..., r1]
+    M = np.zeros((n, cout) + d.shape[2:], np.float32)
+    for c in range(cin):
+        M += U[None, :, c, None, None] * V[:, None, c]
+    at = _AT.astype(np.float32)
+    t2 = np.zeros(M.shape[:4] + (2, 4), np.float32)
+    for i in range(2):
+        t2[..., i, :] = ((at[i, 0] * M[..., 0, :] + at[i, 1] * M[..., 1, :]) + at[i, 2] * M[..., 2, :]) + at[i, 3] * M[..., 3, :]
+    Y = np.zeros(M.shape[:4] + (2, 2), np.float32)
+    for j in range(2):
+        Y[..., j] = ((at[j, 0] * t2[..., 0] + at[j, 1] * t2[..., 1]) + at[j, 2] * t2[..., 2]) + at[j, 3] * t2[..., 3]
+    y = _untile(Y, h, wd)
+    acc = y.transpose(1, 0, 2, 3).reshape(cout, -1)
+    return _epilogue(acc, 1.0, b, slope, act, (n, cout, h, wd))
+
+
+# ---- inputs ---------------------------------------------------------------------------------
+
+FAMILIES = ("uniform", "postact", "small", "nearrange")
+NEAR_SPIKE = 16384.0
+
+
+def make_x(family, shape, rng):
+    """The input families: uniform(-1, 1); post-activation-like (non-negative, sparse, one whole
+    channel zero, signed zeros); small magnitudes (1e-5 .. 1e-3, either sign), where the fp16 lo
+    halves -- below 6.1e-5 the hi halves too -- are subnormal; near the range: uniform(-1, 1) with
+    one activation of 16384 at the last pixel of the last channel of the last frame, which
+    peak_weights() turns into one output near +-65504."""
+    if family == "uniform":
+        return rng.uniform(-1, 1, shape).astype(np.float32)
+    if family == "postact":
+        x = np.maximum(rng.standard_normal(shape), 0) * (rng.uniform(size=shape) < 0.6)
+        x = x.astype(np.float32)
+        x[:, shape[1] // 2] = 0.0
+        x[x == 0] = np.where(rng.uniform(size=int((x == 0).sum())) < 0.5, -0.0, 0.0).astype(np.float32)
+        return x
+    if family == "nearrange":
+        x = rng.uniform(-1, 1, shape).astype(np.float32)
+        x[-1, -1, -1, -1] = NEAR_SPIKE
+        return x
+    if family == "small":
+        return (10.0 ** rng.uniform(-5, -3, shape) * rng.choice([-1.0, 1.0], shape)).astype(np.float32)
+    raise ValueError(family)
+
+
+def make_layer(cin, cout, ks, rng, bias=True):
+    """Filters ~ N(0, 1 / K), bias uniform(-0.1, 0.1), PReLU slopes with negative, zero and > 1
+    entries."""
+    w = (rng.standard_normal((cout, cin, ks, ks)) / np.sqrt(cin * ks * ks)).astype(np.float32)
+    b = (rng.uniform(-0.1, 0.1, cout) if bias else np.zeros(cout)).astype(np.float32)
+    s = rng.uniform(0.05, 0.25, cout).astype(np.float32)
+    s[0] = -0.5
+    if cout > 1:
+        s[cout - 1] = 0.0
+    if cout > 2:
+        s[cout // 2] = 1.75
+    return w, b, s
+
+
+def peak_weights(x, w, b, peak):
+    """The filters with the centre tap of (last output channel, last input channel) set so that the
+    last pixel of the last frame's last channel is `peak` before the activation (x carries
+    NEAR_SPIKE there: the near-range family); every other output stays far below 65504."""
+    w = np.array(w, np.float32)
+    co, ci, p = w.shape[0] - 1, w.shape[1] - 1, w.shape[2] // 2
+    w[co, ci, p, p] = 0.0
+    base = conv64(x[-1:], w[co:co + 1], b[co:co + 1])[0, 0, -1, -1]
+    w[co, ci, p, p] = (peak - base) / float(x[-1, ci, -1, -1])
+    return w
+
+
+def old_bar(y, ref):
+    """The whole-net comparison: max |d| / max |ref|, one number per tensor (bar: < 1e-4)."""
+    y, ref = np.asarray(y, np.float64), np.asarray(ref, np.float64)
+    return float(np.max(np.abs(y - ref)) / max(float(np.max(np.abs(ref))), 1e-30))
+
+
+def worst(y, ref, bound):
+    """max |y - ref| / bound over the elements (<= 1 passes), and where it is."""
+    d = np.abs(np.asarray(y, np.float64) - ref)
+    bound = np.broadcast_to(bound, d.shape)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(bound > 0, d / bound, np.where(d == 0, 0.0, np.inf))
+    r = np.where(np.isnan(r), np.inf, r)             # a NaN in y is no pass
+    i = np.unravel_index(int(np.argmax(r)), r.shape)
+    return float(r[i]), tuple(int(v) for v in i)
+
+
+# ---- mutations: references that are wrong in one local way ----------------------------------
+
+def mutate(kind, x, w, b, slope, act, tile=128):
+    """A float64 result computed wrongly in one local way, as a kernel bug would."""
+    x64, w64 = np.asarray(x, np.float64), np.asarray(w, np.float64)
+    n, cin, h, wd = x.shape
+    cout, ks = w.shape[0], w.shape[2]
+    p = ks // 2
+    pre = conv64(x, w, b)
+    if kind == "corner_tap":            # one tap dropped at one corner pixel of the last frame
+        pre[n - 1, :, h - 1, wd - 1] -= w64[:, :, p, p] @ x64[n - 1, :, h - 1, wd - 1]
+    elif kind == "chunk_pair":          # the last chunk pair (16 channels) skipped for one channel
+        c0 = max(0, (cin - 1) // 16 * 16)
+        co = cout // 2
+        pre[:, co] -= conv64(x[:, c0:], w[co:co + 1, c0:], None)[:, 0]
+    elif kind == "swap_channels":       # two channels of an 8-chunk swapped
+        a, c = min(1, cout - 1), min(5, cout - 1) if cout > 1 else 0
+        pre[:, [a, c]] = pre[:, [c, a]]
+    elif kind == "tile_tail":           # the last pixel of the first tile taken from the next row
+        m = min(tile, h * wd) - 1
+        yy, xx = divmod(m, wd)
+        pre[:, :, yy, xx] = pre[:, :, min(yy + 1, h - 1), xx] if yy + 1 < h else pre[:, :, yy - 1, xx]
+    elif kind == "bias_last":           # bias missing on channel cout - 1
+        pre[:, cout - 1] -= np.float64(b[cout - 1])
+    elif kind == "slope_neighbour":     # PReLU slope of the neighbouring channel
+        assert act == "prelu"
+        return activate(pre, np.roll(np.asarray(slope, np.float64), 1), act)
+    else:
+        raise ValueError(kind)
+    return activate(pre, slope, act)
+
+
+MUTATIONS = ("corner_tap", "chunk_pair", "swap_channels", "tile_tail", "bias_last", "slope_neighbour")
