@@ -547,6 +547,57 @@ typedef struct {
 int isl_augment(const uint8_t* d_src, int n_src, int H, int W, uint8_t* d_dst,
                 const isl_aug_item* items, int m, void* stream);
 
+/* ---- stick-model overlays on resident frames ------------------------------ */
+
+/* One drawing primitive of the stick-model picture the reference writes beside each keypoint
+ * JSON (util.drawStickmodel / draw_bodypose / draw_handpose, src/util.py:47-96,154-185,308-358;
+ * extract_features_mp.py:85-91).  Parity with cv2's polygon rasteriser and matplotlib's
+ * antialiased lines is unpinned (both are absent); DESIGN.md section 4.2j holds this exact integer
+ * definition, which the kernel, islpose.render.apply_numpy and the tests share byte for byte.
+ *
+ * A frame is uint8 [H,W,3]; `color` goes to channels 0, 1, 2 as given (the caller orders it for
+ * RGB or BGR).  A frame's primitives are applied in list order: the blend does not commute.  All
+ * arithmetic is in 64-bit integers; (x, y) is the pixel (column, row), dx = x - cx, dy = y - cy.
+ *   kind 0  stick    p = cx, cy, a, b: half axes a in [1, 4096], b in [1, 16]; c, s =
+ *                    round(cos(t) * 16384), round(sin(t) * 16384) of the angle t, computed by the
+ *                    caller.  u = dx*c + dy*s, v = -dx*s + dy*c; covered iff |u| <= a*2^14 and
+ *                    |v| <= b*2^14 and u^2*b^2 + v^2*a^2 <= a^2*b^2*2^28 (the first two tests
+ *                    come first: they keep the squares under 2^63).
+ *   kind 1  disc     p = cx, cy; covered iff dx^2 + dy^2 <= r2, r2 in [0, 4096].
+ *   kind 2  segment  p = x0, y0, x1, y1, r2 in [0, 4096]: with d = P1 - P0, L2 = d.d,
+ *                    w = (x, y) - P0, t = w.d, cr = w.x*d.y - w.y*d.x, covered iff
+ *                    (L2 > 0 and 0 <= t <= L2 and cr^2 <= r2*L2) or |w|^2 <= r2 or
+ *                    |(x, y) - P1|^2 <= r2.  L2 = 0 is the disc: t and cr are 0 at every pixel
+ *                    then, so the first test is taken only for L2 > 0.
+ *   colouring        a covered channel value v under colour k becomes k (blend 0) or
+ *                    (4*v + 6*k + 5) / 10 rounded down (blend 1), which is rint(0.4*v + 0.6*k)
+ *                    for all 65536 pairs: what cv2.addWeighted(canvas, 0.4, cur, 0.6, 0) leaves
+ *                    inside a limb, while outside it leaves v.
+ * Limits: every coordinate (cx, cy, x0, y0, x1, y1) in [-16384, 16384], |c|, |s| <= 16384,
+ * H, W <= 16384, H*W <= 2^29.  Parts of a primitive off the frame are clipped.  Fields a kind
+ * does not use (a disc's p[2], p[3], c, s; a segment's c, s; a stick's r2) are not read. */
+typedef struct {
+  int32_t kind, p[4], c, s, r2;
+  uint8_t color[3], blend;
+  int32_t reserved;   /* zero */
+} isl_draw_prim;
+
+/* Draws frame f's primitives prims[first[f] .. first[f+1]) onto frame f, for f < n, in one launch
+ * on `stream`: d_src, d_dst uint8 [n,H,W,3] on the current device; `prims` and `first` (n + 1
+ * entries) are host arrays, uploaded stream-ordered through a pinned ring (the call does not wait
+ * for the stream unless eight earlier calls are still in flight).
+ *   d_dst == d_src            in place; a pixel tile no primitive touches is never written
+ *   d_dst disjoint from d_src dst = the copy of src with the drawing
+ *   d_src == NULL             dst = the drawing on an all-zero canvas
+ * n == 0, or no primitives in place: a no-op; no primitives otherwise: the plain copy (or zeros).
+ * ISL_E_ARG, before any device work, for: a NULL d_dst, d_src and d_dst overlapping without being
+ * equal, n < 0, H or W outside [1, 16384], H*W > 2^29, a NULL `first` (n > 0), first[0] != 0, a
+ * decreasing `first`, more than 2^20 primitives, a NULL `prims` with primitives to draw, an
+ * unknown kind, blend not 0 / 1, a parameter a kind reads outside the limits above, or a non-zero
+ * reserved field. */
+int isl_draw(const uint8_t* d_src, uint8_t* d_dst, int n, int H, int W,
+             const isl_draw_prim* prims, const int32_t* first, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

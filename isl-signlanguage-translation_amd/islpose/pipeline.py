@@ -64,6 +64,13 @@ def json_path(out_base: str, label_type: str, expression: str, filename: str, id
     return os.path.join(d, "%s-%d.json" % (filename, idx))
 
 
+def jpg_path(out_base: str, label_type: str, expression: str, filename: str, idx: int,
+             transform: str = "original") -> str:
+    """extract_features_mp.py:91: the stick-model picture beside the JSON, <stem>-<idx>.jpg."""
+    d = os.path.dirname(json_path(out_base, label_type, expression, filename, idx, transform))
+    return os.path.join(d, "%s-%d.jpg" % (filename.split('.')[0], idx))
+
+
 def feature_row(path: str, idx: int, label_type: str, expression: str, feature, transform: str = "original",
                 export: bool = True):
     """The reference's per-frame feature dict (extract_features_mp.py:94-108).  Its
@@ -218,11 +225,38 @@ class KeypointExtractor:
     batch holds `batch` units, its distinct source frames go up once, and one launch
     (islpose.augment.apply; apply_numpy on the host path) builds the batch from them, the
     RGB -> BGR flip folded in.  A variant's JSON goes to <stem>-<transform.name>/ and its row
-    carries transform=name; frames_done and frames_skipped then count units."""
+    carries transform=name; frames_done and frames_skipped then count units.
+
+    write_jpg (False: today's path and outputs, JSON only): also write the reference's stick-model
+    picture of every unit (util.drawStickmodel on the RGB frame, extract_features_mp.py:85-91;
+    islpose/render.py holds the drawing's definition) as <stem>-<idx>.jpg beside its JSON, a
+    variant's in its own <stem>-<transform>/ folder.  On the overlapped path the batch's resident
+    frames stay alive until its results arrive, are drawn by one launch (islpose.render.apply)
+    and come back through pinned memory, all on the writer thread; the other paths draw with
+    render.apply_numpy.
+    jpg_workers threads encode with Pillow at jpg_quality.  A unit then counts as done for
+    resume only when both its files exist."""
 
     def __init__(self, model, out_base: str, batch: int = 64, resume: bool = True, write_json: bool = True,
-                 export: bool = True, overlap=None, transforms=None):
+                 export: bool = True, overlap=None, transforms=None, write_jpg: bool = False, jpg_workers: int = 4,
+                 jpg_quality: int = 75):
         from . import augment
+        self.write_jpg = bool(write_jpg)
+        if self.write_jpg:
+            try:
+                from PIL import Image  # noqa: F401
+            except ImportError:
+                raise ImportError("write_jpg=True encodes the pictures with Pillow (PIL), which is not installed")
+            if isinstance(jpg_workers, bool) or not isinstance(jpg_workers, int) or jpg_workers < 1:
+                raise ValueError("jpg_workers must be an integer >= 1, got %r" % (jpg_workers,))
+            if isinstance(jpg_quality, bool) or not isinstance(jpg_quality, int) or not 1 <= jpg_quality <= 95:
+                raise ValueError("jpg_quality must be an integer in [1, 95], got %r" % (jpg_quality,))
+            self.jpg_workers, self.jpg_quality = jpg_workers, jpg_quality
+            self._jpg_pool = None
+            # wall seconds per stage of the pictures, all on the thread that writes: building the
+            # primitives; the draw and the copy back; waiting for the encoders after the batch's
+            # JSON files and rows are written (the encoders run beside those)
+            self.jpg_seconds = {"primitives": 0.0, "draw_copy": 0.0, "encode_wait": 0.0}
         self.transforms = None if transforms is None else augment.check_transforms(transforms)
         self.model = model
         self.export = export
@@ -234,26 +268,100 @@ class KeypointExtractor:
         self.frames_done = 0
         self.frames_skipped = 0
 
+    def _done(self, filename, label_type, expression, idx, name="original"):
+        """Resume's test of one unit: its JSON exists -- and, with write_jpg, its picture
+        (the reference needs both, src/dataloader.py:91-95)."""
+        if not os.path.exists(json_path(self.out_base, label_type, expression, filename, idx, name)):
+            return False
+        return not self.write_jpg or os.path.exists(jpg_path(self.out_base, label_type, expression, filename, idx, name))
+
     def _todo(self, filename, frames, label_type, expression):
         todo = []
         for idx in range(len(frames)):
-            p = json_path(self.out_base, label_type, expression, filename, idx)
-            if self.resume and os.path.exists(p):
+            if self.resume and self._done(filename, label_type, expression, idx):
                 self.frames_skipped += 1
                 continue
             todo.append(idx)
         return todo
 
-    def _write(self, rows, filename, label_type, expression, ids, feats):
-        for idx, feat in zip(ids, feats):
+    @staticmethod
+    def _primitives(feats):
+        from . import render
+        return [render.body_primitives(f[0], f[1], "body25") + render.hand_primitives(f[2]) for f in feats]
+
+    def _save_jpg(self, path, rgb):
+        from PIL import Image
+        Image.fromarray(rgb).save(path, format="JPEG", quality=self.jpg_quality)
+
+    def _write(self, rows, filename, label_type, expression, ids, feats, pics=None):
+        """pics (write_jpg): a callable returning the units' drawn RGB frames as uint8
+        [n, H, W, 3] on the host, valid until the next call."""
+        jobs = []
+        if pics is not None:
+            pics = pics()
+            if self._jpg_pool is None:
+                from concurrent.futures import ThreadPoolExecutor
+                self._jpg_pool = ThreadPoolExecutor(self.jpg_workers)
+        for k, (idx, feat) in enumerate(zip(ids, feats)):
             # a unit of the augmented path is (frame index, transform name)
             idx, name = idx if isinstance(idx, tuple) else (idx, "original")
             p = json_path(self.out_base, label_type, expression, filename, idx, name)
-            if self.write_json:
+            if self.write_json or pics is not None:
                 os.makedirs(os.path.dirname(p), exist_ok=True)
+            if self.write_json:
                 with open(p, "w") as f:
                     f.write(frame_json(*feat))
+            if pics is not None:
+                jobs.append(self._jpg_pool.submit(self._save_jpg, jpg_path(self.out_base, label_type, expression,
+                                                                          filename, idx, name), pics[k]))
             rows.append(feature_row(p, idx, label_type, expression, feat, transform=name, export=self.export))
+        t0 = time.perf_counter()
+        for j in jobs:
+            j.result()
+        if jobs:
+            self.jpg_seconds["encode_wait"] += time.perf_counter() - t0
+
+    def _host_pics(self, rgb, feats):
+        """The host path's pictures: render.apply_numpy on the units' RGB frames."""
+        from . import render
+
+        def pics():
+            t0 = time.perf_counter()
+            lists = self._primitives(feats)
+            t1 = time.perf_counter()
+            out = render.apply_numpy(rgb, lists)
+            self.jpg_seconds["primitives"] += t1 - t0
+            self.jpg_seconds["draw_copy"] += time.perf_counter() - t1
+            return out
+        return pics
+
+    def _device_pics(self, rgb_t, feats):
+        """The overlapped path's pictures, made on the writer thread beside the next batch's
+        model pass: the primitives, one launch on the batch's resident RGB frames (whose upload
+        the arrived results prove complete) on a stream of the writer's own, and the copy into a
+        pinned buffer, which the writer reuses batch after batch: it encodes one batch at a time."""
+        import torch
+        from . import render
+
+        def pics():
+            t0 = time.perf_counter()
+            lists = self._primitives(feats)
+            t1 = time.perf_counter()
+            dev = rgb_t.device
+            if getattr(self, "_jpg_stream", None) is None:
+                self._jpg_stream, self._jpg_pin = torch.cuda.Stream(device=dev), None
+            with torch.cuda.device(dev), torch.cuda.stream(self._jpg_stream):
+                drawn = render.apply(rgb_t, lists, stream=self._jpg_stream)
+                need = drawn.numel()
+                if self._jpg_pin is None or self._jpg_pin.numel() < need:
+                    self._jpg_pin = torch.empty(need, dtype=torch.uint8, pin_memory=True)
+                host = self._jpg_pin[:need].view(drawn.shape)
+                host.copy_(drawn, non_blocking=True)
+                self._jpg_stream.synchronize()
+            self.jpg_seconds["primitives"] += t1 - t0
+            self.jpg_seconds["draw_copy"] += time.perf_counter() - t1
+            return host.numpy()
+        return pics
 
     def _aug_batches(self, videos):
         """_batches with transforms: per batch ((rows, filename, label_type, expression, units,
@@ -267,8 +375,7 @@ class KeypointExtractor:
             todo = []
             for idx in range(len(frames)):
                 for k, name in enumerate(["original"] + [t.name for t in self.transforms]):
-                    if self.resume and os.path.exists(json_path(self.out_base, label_type, expression, filename,
-                                                                 idx, name)):
+                    if self.resume and self._done(filename, label_type, expression, idx, name):
                         self.frames_skipped += 1
                         continue
                     todo.append((idx, k - 1, name))
@@ -316,19 +423,26 @@ class KeypointExtractor:
             from . import augment
             for (rows, filename, lt, ex, units, items), sel in self._aug_batches(vids):
                 bgr = augment.apply_numpy(sel, items, swap_rb=True)
-                self._write(rows, filename, lt, ex, units, self.model.call_batch(bgr))
+                feats = self.model.call_batch(bgr)
+                self._write(rows, filename, lt, ex, units, feats,
+                            self._host_pics(bgr[..., ::-1], feats) if self.write_jpg else None)
                 self.frames_done += len(units)
             return out
         if not overlap:
             for (rows, filename, lt, ex, ids), sel in self._batches(vids):
                 # model(frame[:, :, ::-1]): the reference feeds BGR (extract_features_mp.py:124)
                 bgr = np.ascontiguousarray(np.asarray(sel)[..., ::-1])
-                self._write(rows, filename, lt, ex, ids, self.model.call_batch(bgr))
+                feats = self.model.call_batch(bgr)
+                self._write(rows, filename, lt, ex, ids, feats,
+                            self._host_pics(np.asarray(sel), feats) if self.write_jpg else None)
                 self.frames_done += len(ids)
             return out
         dev = getattr(self.model, "_device", None)
         dev = torch.cuda.current_device() if dev is None else dev
         writer = _Writer(self._write)
+
+        import collections
+        held = collections.deque()        # write_jpg: each batch's resident RGB units, in order
 
         def bgr_batches():
             if self.transforms is not None:
@@ -336,9 +450,14 @@ class KeypointExtractor:
                 for meta, rgb in _Prefetch(self._aug_batches(vids), dev):
                     # the batch's units from its resident source frames, in one launch; swap_rb
                     # is the flip of extract_features_mp.py:124
-                    yield meta[:5], augment.apply(rgb, meta[5], swap_rb=True)
+                    bgr = augment.apply(rgb, meta[5], swap_rb=True)
+                    if self.write_jpg:
+                        held.append(bgr.flip(-1))             # the units as the RGB pictures' canvases
+                    yield meta[:5], bgr
                 return
             for meta, rgb in _Prefetch(self._batches(vids), dev):
+                if self.write_jpg:
+                    held.append(rgb)
                 yield meta, rgb.flip(-1)                      # extract_features_mp.py:124, on the GPU
 
         # models with the pipelined form (ISLSignPos.call_batches) overlap the body of
@@ -348,7 +467,10 @@ class KeypointExtractor:
             batches = lambda it: ((meta, self.model.call_batch(bgr)) for meta, bgr in it)  # noqa: E731
         try:
             for (rows, filename, lt, ex, ids), feats in batches(bgr_batches()):
-                writer.put(rows, filename, lt, ex, ids, feats)
+                if self.write_jpg:
+                    writer.put(rows, filename, lt, ex, ids, feats, self._device_pics(held.popleft(), feats))
+                else:
+                    writer.put(rows, filename, lt, ex, ids, feats)
                 self.frames_done += len(ids)
         finally:
             writer.close()
@@ -360,12 +482,12 @@ class KeypointExtractor:
 
 def extract_dataset(rows, decode, model, out_base: str, rank: int = 0, world: int = 1, batch: int = 64,
                     resume: bool = True, write_json: bool = True, export: bool = True, overlap=None,
-                    transforms=None):
+                    transforms=None, **jpg):
     """rows: [{'Filepath', 'type', 'expression'}] (the dataset CSV of extract_features_mp.py:187).
     Videos are sharded contiguously across ranks; returns (this rank's feature rows, extractor)."""
     start, end = shard_bounds(len(rows), rank, world)
     ex = KeypointExtractor(model, out_base, batch=batch, resume=resume, write_json=write_json, export=export,
-                           overlap=overlap, transforms=transforms)
+                           overlap=overlap, transforms=transforms, **jpg)
     videos = [(r['Filepath'].split('/')[-1], (lambda fp=r['Filepath']: decode(fp)), r['type'], r['expression'])
               for r in rows[start:end]]
     out = []
@@ -388,12 +510,12 @@ def read_dataset_csv(path: str):
 
 
 def run(rows, decode, model, out_base: str, rank: int, world: int, batch: int = 64, resume: bool = True,
-        write_json: bool = True, group=None, export: bool = True, overlap=None, transforms=None):
+        write_json: bool = True, group=None, export: bool = True, overlap=None, transforms=None, **jpg):
     """One rank's share + the host-side gather; rank 0 writes the combined CSV like the
     reference's __main__ (extract_features_mp.py:225-239). Returns (rows on rank 0 or None, stats)."""
     t0 = time.time()
     feats, ex = extract_dataset(rows, decode, model, out_base, rank, world, batch, resume, write_json, export,
-                                overlap, transforms)
+                                overlap, transforms, **jpg)
     dt = time.time() - t0
     stamp = datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
     save_features_csv(feats, os.path.join(out_base, "output_%d_exectime-%.4f_%s.csv" % (rank, dt, stamp)))

@@ -126,6 +126,7 @@ EXPORTS = ["isl_abi_version", "isl_last_error", "isl_net_create", "isl_net_destr
            "isl_net_get_act_storage", "isl_net_act_storage_active", "isl_post_opts_default",
            "isl_body_post_opts", "isl_hand_post_opts", "isl_hand_post_crops_opts",
            "isl_net_preprocess_crops_flip", "isl_hand_post_ex", "isl_hand_post_crops_ex", "isl_augment",
+           "isl_draw",
            "isl_debug_conv3x3", "isl_debug_conv"]
 
 
@@ -159,6 +160,14 @@ class IslAugItem(ctypes.Structure):
     _fields_ = [("c", ctypes.c_double), ("s", ctypes.c_double), ("src", ctypes.c_int32),
                 ("rotate", ctypes.c_int32), ("threshold", ctypes.c_int32), ("swap_rb", ctypes.c_int32),
                 ("reserved", ctypes.c_int32 * 2)]
+
+
+class IslDrawPrim(ctypes.Structure):
+    """isl_draw_prim: kind 0 stick (p = cx, cy, a, b; c, s), 1 disc (p = cx, cy; r2), 2 segment
+    (p = x0, y0, x1, y1; r2); color for channels 0, 1, 2; blend 0 / 1; reserved zero."""
+    _fields_ = [("kind", ctypes.c_int32), ("p", ctypes.c_int32 * 4), ("c", ctypes.c_int32), ("s", ctypes.c_int32),
+                ("r2", ctypes.c_int32), ("color", ctypes.c_uint8 * 3), ("blend", ctypes.c_uint8),
+                ("reserved", ctypes.c_int32)]
 
 
 class IslDebugSeg(ctypes.Structure):
@@ -334,6 +343,7 @@ def lib():
     L.isl_hand_post_ex.argtypes = L.isl_hand_post_opts.argtypes + [pu8, vp]
     L.isl_hand_post_crops_ex.argtypes = L.isl_hand_post_crops_opts.argtypes + [pu8, vp]
     L.isl_augment.argtypes = [vp, i32, i32, i32, vp, ctypes.POINTER(IslAugItem), i32, vp]
+    L.isl_draw.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(IslDrawPrim), ctypes.POINTER(i32), vp]
     L.isl_debug_conv3x3.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]
     L.isl_debug_conv.argtypes = [ctypes.POINTER(IslDebugConvDesc), vp, vp, vp, vp, vp, vp,
                                  ctypes.POINTER(IslDebugConvResult)]
@@ -390,6 +400,22 @@ def augment(src_u8, items, out=None, stream=None):
         s = stream if stream is not None else torch.cuda.current_stream(src_u8.device)
         check(lib().isl_augment(ptr(src_u8), n, H, W, ptr(out), arr, m, ctypes.c_void_p(s.cuda_stream)), "isl_augment")
     return out
+
+
+def draw(src_u8, dst_u8, prims, first, stream=None):
+    """isl_draw: dst_u8 cuda uint8 [n, H, W, 3] (contiguous) receives src_u8 (the same tensor: in
+    place; another of the same shape: a copy; None: an all-zero canvas) with frame f's primitives
+    prims[first[f]:first[f + 1]] drawn in list order, in one launch on `stream` (None: the
+    current stream of the destination's device).  prims: a ctypes array of IslDrawPrim (or None
+    when first[n] == 0); first: n + 1 ints."""
+    import torch
+    n, H, W, _ = dst_u8.shape
+    arr = (ctypes.c_int32 * (n + 1))(*first)
+    with torch.cuda.device(dst_u8.device):
+        s = stream if stream is not None else torch.cuda.current_stream(dst_u8.device)
+        check(lib().isl_draw(None if src_u8 is None else ptr(src_u8), ptr(dst_u8), n, H, W, prims, arr,
+                             ctypes.c_void_p(s.cuda_stream)), "isl_draw")
+    return dst_u8
 
 
 def body_layout(kind: int, caps: IslCaps) -> IslLayout:

@@ -211,6 +211,37 @@ class ISLSignPos(object):
         names = ["original"] + [tr.name for tr in ts]
         return {name: res[j * n:(j + 1) * n] for j, name in enumerate(names)}
 
+    @staticmethod
+    def render_primitives(results, hands=True):
+        """One primitive list per call_batch result (islpose.render): the body's sticks and
+        joints in util.drawStickmodel's order, then the hands' edges and peaks."""
+        from islpose import render
+        return [render.body_primitives(r[0], r[1], "body25") + (render.hand_primitives(r[2]) if hands else [])
+                for r in results]
+
+    def render(self, frames, results, hands=True, blank=False):
+        """The stick-model pictures of util.drawStickmodel (util.py:308-358; islpose.render holds
+        the definition and its deviations): frames uint8 [n, H, W, 3] (host or cuda; the colours
+        go to channels 0, 1, 2 as the reference's table gives them), results what call_batch
+        returned for them -> the frames with each result drawn, as a new array (a cuda tensor
+        for cuda frames, else numpy).  One isl_draw launch when a GPU is there, apply_numpy
+        otherwise.  blank: draw on an all-zero canvas of the frames' shape instead."""
+        from islpose import render
+        lists = self.render_primitives(results, hands)
+        on_dev = isinstance(frames, torch.Tensor) and frames.is_cuda
+        if not on_dev and not torch.cuda.is_available():
+            a = np.ascontiguousarray(_as_numpy(frames), dtype=np.uint8)
+            return render.apply_numpy(None if blank else a, lists, shape=a.shape)
+        if on_dev:
+            if frames.dtype != torch.uint8:
+                raise ValueError("frames: uint8 [n, H, W, 3] expected, got %s" % (frames.dtype,))
+            t = frames.contiguous()
+        else:
+            dev = self._device if self._device is not None else torch.cuda.current_device()
+            t = torch.from_numpy(np.ascontiguousarray(_as_numpy(frames), dtype=np.uint8)).to("cuda:%d" % dev)
+        out = render.apply(None if blank else t, lists, shape=tuple(t.shape), device=t.device)
+        return out if on_dev else out.cpu().numpy()
+
     def hands_for(self, frames_t, body_results, ests=None, defer=False):
         """Everything after the body: frames_t cuda uint8 [n, H, W, 3], body_results
         [(candidate, subset)] * n -> the results of call_batch: util.hand_boxes per frame (in

@@ -146,6 +146,7 @@ def c5(args):
     from src.hand import Hand
     from src.ISL_Model_parameter import ISLSignPos
     transforms = augment.parse_spec(args.augment, seed=args.augment_seed)
+    jpg = {"write_jpg": True, "jpg_workers": args.jpg_workers} if args.write_jpg else {}
     per_frame = 1 + len(transforms or ())
     T, H, W = args.c5_frames, 1080, 1920
     B = args.c5_batch
@@ -165,6 +166,7 @@ def c5(args):
            "videos": len(rows), "batch": B, "export": False, "max_people": args.max_people,
            "hand_scales": list(isl.hand_opts["hand_scales"]), "flip_left": bool(args.flip_left),
            "augment": args.augment or None, "units_per_frame": per_frame,
+           "write_jpg": bool(args.write_jpg), "jpg_workers": args.jpg_workers if args.write_jpg else None,
            "decode": "frames already decoded in host memory (pims/ffmpeg absent); the pipeline reads them as "
                      "slices of the [T,H,W,3] array"}
     for ov in ((True,) if args.c5_overlap_only else (False, True)):
@@ -172,12 +174,12 @@ def c5(args):
         try:
             # warm-up (arenas, hand scales) on the first video, then the timed pass over all
             pipeline.extract_dataset(rows[:1], clips.__getitem__, isl, out, batch=B, export=False, overlap=ov,
-                                     transforms=transforms)
+                                     transforms=transforms, **jpg)
             shutil.rmtree(out)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             feats, ex = pipeline.extract_dataset(rows, clips.__getitem__, isl, out, batch=B,
-                                                 export=False, overlap=ov, transforms=transforms)
+                                                 export=False, overlap=ov, transforms=transforms, **jpg)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             hands = peaks = 0
@@ -191,6 +193,8 @@ def c5(args):
         res[key + "_units_per_s"] = round(ex.frames_done / dt, 2)
         res[key + "_frames_per_s"] = round(ex.frames_done / per_frame / dt, 2)
         res[key + "_s"] = round(dt, 3)
+        if args.write_jpg:
+            res[key + "_jpg_stage_s"] = {k: round(v, 3) for k, v in ex.jpg_seconds.items()}
         res["hand_crops_per_frame"] = round(hands / max(len(feats), 1), 2)     # (per unit with --augment)
         res["body_peaks_per_frame"] = round(peaks / max(len(feats), 1), 2)
     return res
@@ -313,6 +317,70 @@ def hands2(args):
             "hand_scales": list(isl.hand_opts["hand_scales"]), "flip_left": bool(args.flip_left)}
 
 
+def render(args):
+    """isl_draw on 64 resident 1080x1920 frames, each with HANDS2's designed arms (plus neck, nose
+    and mid-hip) and two designed hands (their 21 peaks spread over the two hand boxes): ms per batch in place, out of
+    place and on the blank canvas (HIP events around `steps` launches with a prebuilt table, so
+    the figure is the upload of the table plus the kernel), out-of-place bytes per second against
+    the 2*H*W*3 floor beside isl_augment's plain copy of the same frames on the same box, the wall
+    time of islpose.render.apply (which also builds the records), and apply_numpy per frame."""
+    from islpose import augment, render as rd, runtime as rt, synth
+    from src import util
+    B, H, W = 64, 1080, 1920
+    pts = {2: (800, 300), 3: (700, 500), 4: (700, 700), 5: (1100, 300), 6: (1200, 500), 7: (1200, 700),
+           1: (950, 280), 0: (950, 180), 8: (950, 640)}
+    cand = np.array([[x, y, 0.9, k] for k, (x, y) in enumerate(pts.values())], np.float64)
+    sub = -np.ones((1, 27))
+    for k, j in enumerate(pts):
+        sub[0, j] = k
+    sub[0, -2], sub[0, -1] = len(pts) * 0.9, len(pts)
+    frames = torch.from_numpy(synth.synth_frames(B, H, W, seed=57)).cuda()
+    hands = []
+    for x, y, w, _left, _row in util.hand_boxes(cand, sub, frames[0]):
+        rng = np.random.RandomState(x)
+        hands.append(np.stack([x + rng.randint(10, w - 10, 21), y + rng.randint(10, w - 10, 21)], axis=1).astype(np.int64))
+    one = rd.body_primitives(cand, sub, "body25") + rd.hand_primitives(hands)
+    lists = [one] * B
+    flat = [rt.IslDrawPrim(q.kind, q.p, q.c, q.s, q.r2, q.color, q.blend, 0) for lst in lists for q in lst]
+    arr = (rt.IslDrawPrim * len(flat))(*flat)
+    first = [len(one) * f for f in range(B + 1)]
+    work, dst = frames.clone(), torch.empty_like(frames)
+    reps = max(args.steps, 1) * 10
+
+    def events(step):
+        for _ in range(max(args.warmup, 10)):      # (past the eight table slots' first-use allocations)
+            step()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            step()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    ms_in = events(lambda: rt.draw(work, work, arr, first))
+    ms_out = events(lambda: rt.draw(frames, dst, arr, first))
+    ms_blank = events(lambda: rt.draw(None, dst, arr, first))
+    copies = [rt.IslAugItem(1.0, 0.0, i, 0, 256, 0) for i in range(B)]
+    ms_copy = events(lambda: rt.augment(frames, copies, out=dst))
+    wall = timed(lambda: rd.apply(frames, lists, out=dst), args.steps, args.warmup)
+    host = frames[:1].cpu().numpy()
+    t0 = time.perf_counter()
+    ref = rd.apply_numpy(host, lists[:1])
+    t_np = time.perf_counter() - t0
+    same = bool(np.array_equal(rd.apply(frames[:1].contiguous(), lists[:1]).cpu().numpy(), ref))
+    floor = 2.0 * H * W * 3 * B
+    tiles = ((W + 127) // 128) * ((H + 15) // 16)
+    return {"config": "RENDER isl_draw on 64 resident 1080x1920 frames, one designed person and two hands each",
+            "frames": B, "prims_per_frame": len(one), "launches_timed": reps,
+            "in_place_ms": round(ms_in, 4), "out_of_place_ms": round(ms_out, 4), "blank_ms": round(ms_blank, 4),
+            "floor_bytes": floor, "out_of_place_tb_per_s": round(floor / ms_out / 1e9, 3),
+            "augment_copy_ms": round(ms_copy, 4), "augment_copy_tb_per_s": round(floor / ms_copy / 1e9, 3),
+            "apply_wall_ms": round(wall * 1e3, 3), "apply_numpy_ms_per_frame": round(t_np * 1e3, 2),
+            "gpu_equals_apply_numpy": same, "tiles_per_frame": tiles,
+            "basis": "HIP events around the timed launches on one stream, each launch with its table upload"}
+
+
 def c6(args):
     from islpose import synth, translate
     from src.body import Body
@@ -350,7 +418,7 @@ def c6(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", choices=["c3", "c4", "c5", "c6", "frame", "hands2", "all"], default="all")
+    ap.add_argument("--config", choices=["c3", "c4", "c5", "c6", "frame", "hands2", "render", "all"], default="all")
     ap.add_argument("--frame-count", type=int, default=64, help="FRAME: sequential per-frame calls timed")
     ap.add_argument("--frame-repeat", type=int, default=4, help="FRAME: timed passes over the frames")
     ap.add_argument("--batch", type=int, default=16, help="C3 / C4 frames per step")
@@ -383,6 +451,9 @@ def main():
                     help="C5: augmented variants per frame, e.g. rotation:30,solarize:192 (RandomRotation / "
                          "RandomSolarize, islpose.augment.parse_spec); default: none")
     ap.add_argument("--augment-seed", type=int, default=0, help="C5: seed of the --augment draws")
+    ap.add_argument("--write-jpg", action="store_true",
+                    help="C5: also write every frame's stick-model JPEG (KeypointExtractor write_jpg)")
+    ap.add_argument("--jpg-workers", type=int, default=4, help="C5: JPEG encoder threads of --write-jpg")
     a = ap.parse_args()
     a.hand_scales = tuple(float(v) for v in a.hand_scales.split(",")) if a.hand_scales else None
     if a.precision:
@@ -390,7 +461,7 @@ def main():
     if a.act_storage:
         os.environ["ISLPOSE_ACT_STORAGE"] = a.act_storage
     for name, fn in (("c3", c3), ("c4", c4), ("c5", c5), ("c6", c6), ("frame", frame),
-                     ("hands2", hands2)):
+                     ("hands2", hands2), ("render", render)):
         if a.config in (name, "all"):
             res = fn(a)
             res["precision"] = os.environ.get("ISLPOSE_PRECISION", "fp32")

@@ -62,6 +62,11 @@ def main():
                          "extract_featuressingle.py does: comma-separated rotation:DEGREES (RandomRotation) and "
                          "solarize:THRESHOLD[:P] (RandomSolarize), e.g. rotation:30,solarize:192; each goes to "
                          "<stem>-<TransformClassName>/ with its name in the row's transform column")
+    ap.add_argument("--write-jpg", action="store_true",
+                    help="also write the reference's stick-model picture of every frame (extract_features_mp.py:"
+                         "85-91) as <stem>-<idx>.jpg beside its JSON; needs Pillow")
+    ap.add_argument("--jpg-workers", type=int, default=4, help="JPEG encoder threads of --write-jpg")
+    ap.add_argument("--jpg-quality", type=int, default=75, help="JPEG quality of --write-jpg (Pillow's default 75)")
     ap.add_argument("--augment-seed", type=int, default=0,
                     help="seed of the --augment draws (per frame: seed, video name, frame index, position)")
     a = ap.parse_args()
@@ -107,7 +112,9 @@ def main():
     t0 = time.time()
     merged, stats = pipeline.run(rows, decode, model, a.out, rank, world, batch=a.batch,
                                  resume=not a.no_resume, write_json=not a.no_json, group=group,
-                                 export=not a.no_export, transforms=transforms)
+                                 export=not a.no_export, transforms=transforms,
+                                 **({"write_jpg": True, "jpg_workers": a.jpg_workers, "jpg_quality": a.jpg_quality}
+                                    if a.write_jpg else {}))
     # (with --augment the extractor's count is units: frames times 1 + the number of transforms)
     stats["units_per_frame"] = 1 + len(transforms or ())
     stats["frames_per_s"] = stats["frames"] / stats["units_per_frame"] / max(time.time() - t0, 1e-9)
