@@ -108,7 +108,9 @@ int isl_net_set_param(isl_net* net, const char* caffe_name, const float* host, i
 
 /* Replaces `model.forward(x)`: x is float32 NCHW [n,3,h,w] on the device.
  * body25/coco: out0 = PAF [n,npaf,h/8,w/8], out1 = heat [n,njoint,h/8,w/8];
- * hand: out0 = heat [n,22,h/8,w/8], out1 must be NULL.  (floor-mode pooling.) */
+ * hand: out0 = heat [n,22,h/8,w/8], out1 must be NULL.  (floor-mode pooling.)
+ * With ISL_ALGO_X3 an element of x outside the fp16 split range -- !(|x| < 65504): too large,
+ * +-inf or NaN -- raises the range flag (isl_net_check), like a conv output that leaves it. */
 int isl_net_forward(isl_net* net, const float* d_x_nchw, int n, int h, int w,
                     float* d_out0, float* d_out1, void* stream);
 
@@ -233,7 +235,10 @@ int isl_lane_stream_destroy(void* stream);
  * conv output since the last clear left the fp16 split range (the results of
  * those runs are then not fp32-accurate and must be recomputed with
  * ISL_ALGO_DIRECT), else ISL_OK; clear != 0 resets the flag.  The post records
- * of isl_body_post carry the same flag in their status word without a sync. */
+ * of isl_body_post carry the same flag in their status word without a sync.
+ * The flag also rises where nothing stored left the range but an intermediate did: a Winograd
+ * input transform (up to 4 x the activations) that overflows the split, whatever the activation
+ * then stores, and an isl_net_forward input outside the range. */
 int isl_net_check(isl_net* net, int clear);
 /* The same check stream-ordered, for pipelined callers: enqueues on `stream` a copy of
  * the flag into *h_flag (pinned host memory; valid once the stream has reached it) and

@@ -223,7 +223,9 @@ conv_mfma_f32(ConvArgs a) {
                    acc[wm][wn][4 * q + 2] + b[2], acc[wm][wn][4 * q + 3] + b[3]};
         if (a.act == ACT_RELU) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+          // (v <= 0 ? 0 : v, not v > 0 ? v : 0: the same bits for every number, and a NaN stays a
+          // NaN as in torch -- these kernels are the range guard's fallback and take every input)
+          for (int e = 0; e < 4; ++e) v[e] = v[e] <= 0.f ? 0.f : v[e];
         } else if (a.act == ACT_PRELU) {
           const f32x4 sl = *(const f32x4*)(a.slope + co);
 #pragma unroll

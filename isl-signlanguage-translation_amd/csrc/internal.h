@@ -207,7 +207,8 @@ hipError_t launch_range_count(const int* flag, unsigned long long* trips, hipStr
 hipError_t launch_vpool2(const Act& half, const Act& out, int C, hipStream_t s);
 // (both pools take fp16 buffers too -- in and out of one Act::esize; the max of roundings is
 // the rounding of the max)
-hipError_t launch_pack_nchw(const float* x, int n, int C, int h, int w, const Act& out, hipStream_t s);
+// range_flag: raised for an input element outside the fp16 split range (null: no check kept)
+hipError_t launch_pack_nchw(const float* x, int n, int C, int h, int w, const Act& out, int* range_flag, hipStream_t s);
 hipError_t launch_unpack_nchw(const Act& in, int coff, int C, float* y, hipStream_t s);
 // Pre-processing of a batch of images described by a device table of entries
 // (preprocess_entry: byte offset of the image in `frames`, its size, the

@@ -28,7 +28,12 @@ __global__ void maxpool2_kernel(const float* __restrict__ in, int ip, int iH, in
   const f32x4 c = *(const f32x4*)(p + (size_t)iWp * 8), d = *(const f32x4*)(p + (size_t)iWp * 8 + 8);
   f32x4 m;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) m[e] = fmaxf(fmaxf(a[e], b[e]), fmaxf(c[e], d[e]));
+  for (int e = 0; e < 4; ++e) {
+    m[e] = fmaxf(fmaxf(a[e], b[e]), fmaxf(c[e], d[e]));
+    // fmaxf drops a NaN, MaxPool2d keeps it: this is the pool of the fp32 fallback, which takes
+    // every input (the split-fp16 paths raise the range flag for a NaN before it reaches a pool)
+    if (__builtin_isunordered(a[e], b[e]) || __builtin_isunordered(c[e], d[e])) m[e] = __builtin_nanf("");
+  }
   *(f32x4*)(out + ((size_t)f * out_chunks + k) * och + (size_t)((y + op) * oWp + x + op) * 8 + 4 * half) = m;
 }
 
@@ -143,26 +148,34 @@ hipError_t launch_vpool2(const Act& in, const Act& out, int C, hipStream_t s) {
 }
 
 // NCHW float (module seam input) -> chunked padded buffer, channels >= C zero-filled.
+// range_flag (the split-fp16 convs' guard, or null): raised for an element outside the fp16 split
+// range, !(|x| < 65504) -- too large, +-inf or NaN.  The first conv would split it to inf / NaN
+// and its ReLU store 0 without a flag; this is the one read of the caller's tensor.
 __global__ void pack_nchw_kernel(const float* __restrict__ x, int n, int C, int h, int w,
-                                 float* __restrict__ out, int op, int ocs) {
+                                 float* __restrict__ out, int op, int ocs, int* __restrict__ range_flag) {
   const long long total = (long long)n * h * w;
   const size_t chs = (size_t)(h + 2 * op) * (w + 2 * op) * 8;
+  bool bad = false;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
        i += (long long)gridDim.x * blockDim.x) {
     const int xx = (int)(i % w);
     const int yy = (int)((i / w) % h);
     const int f = (int)(i / ((long long)w * h));
     float* o = out + (size_t)f * (ocs / 8) * chs + ((size_t)(yy + op) * (w + 2 * op) + xx + op) * 8;
-    for (int c = 0; c < ocs; ++c)
-      o[(size_t)(c >> 3) * chs + (c & 7)] = c < C ? x[(((size_t)f * C + c) * h + yy) * w + xx] : 0.f;
+    for (int c = 0; c < ocs; ++c) {
+      const float v = c < C ? x[(((size_t)f * C + c) * h + yy) * w + xx] : 0.f;
+      bad |= !(__builtin_fabsf(v) < 65504.f);
+      o[(size_t)(c >> 3) * chs + (c & 7)] = v;
+    }
   }
+  if (bad && range_flag) atomicOr(range_flag, 1);
 }
 
-hipError_t launch_pack_nchw(const float* x, int n, int C, int h, int w, const Act& out, hipStream_t s) {
+hipError_t launch_pack_nchw(const float* x, int n, int C, int h, int w, const Act& out, int* range_flag, hipStream_t s) {
   const long long total = (long long)n * h * w;
   const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 16);
   if (out.esize != 4) { set_error("pack_nchw: the net input is an fp32 buffer"); return hipErrorInvalidValue; }
-  hipLaunchKernelGGL(pack_nchw_kernel, dim3(grid), dim3(256), 0, s, x, n, C, h, w, out.base, out.pad, out.cs);
+  hipLaunchKernelGGL(pack_nchw_kernel, dim3(grid), dim3(256), 0, s, x, n, C, h, w, out.base, out.pad, out.cs, range_flag);
   return hipGetLastError();
 }
 

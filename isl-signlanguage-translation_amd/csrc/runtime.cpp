@@ -2160,7 +2160,9 @@ int isl_net_forward(isl_net* net, const float* d_x, int n, int h, int w, float* 
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   if ((rc = plan(net, n, h, w, s))) return rc;
-  HIP_OK(launch_pack_nchw(d_x, n, 3, h, w, net->act[net->in_buf], s));
+  // the split-fp16 convs take |x| < 65504: the pack raises the range flag for anything else in the
+  // caller's tensor (the fp32 kernels of the fallback take every value and raise nothing)
+  HIP_OK(launch_pack_nchw(d_x, n, 3, h, w, net->act[net->in_buf], net->algo == ISL_ALGO_X3 ? net->d_flag : nullptr, s));
   if ((rc = run_ops(net, s))) return rc;
   return copy_outputs(net, d_out0, d_out1, s);
 }

@@ -346,9 +346,13 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[x][i][j][r] = 0.f;
-  // Range: a V value with |V| >= 65520 splits to an infinite hi, which makes every output it feeds
-  // inf or NaN (a zero filter gives NaN too), so the epilogue's output check raises the range flag
-  // (the host then recomputes on the fp32 kernels); |V| in [65504, 65520) splits exactly.
+  // Range: V = B^T d B reaches 4 x the input, so inputs below 65504 can give |V| >= 65520.  Such
+  // a V splits to hi = +-inf and lo = v - hi = -+inf; the three products hi Uhi + lo Uhi + hi Ulo
+  // are inf - inf (0 inf for a zero filter), so every output fed by that V is NaN, for every
+  // output channel.  A ReLU would store that NaN as 0: the epilogue therefore tests the value
+  // before the activation for NaN / inf and the stored value for its magnitude, and either
+  // raises the range flag (the host then recomputes on the fp32 kernels).  |V| in [65504, 65520)
+  // splits exactly.
 
   // PF = 1: the K step's four (tile half j, channel quad Q) groups in the order (0, 0), (0, 1),
   // (1, 0), (1, 1), the same V values, splits and MFMAs as below in the same order.  The six
@@ -637,6 +641,7 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
   // epilogue: M tiles through LDS, per round i (32 channels) [xi][j][q][h][32] x f32x4 (128 KB);
   // thread (j, q, h, tile) sums its 4 channels' 16 values in a fixed order into the 2x2 outputs
   f32x4* xm = smem;
+  f32x4 nonfin = {0.f, 0.f, 0.f, 0.f};   // NaN where a value in front of the activation was NaN or +-inf
   const float* eb = (const float*)(smem + 8192);
   const int Wo = a.W + 2 * a.out_pad;
   float* out_f = a.out + (size_t)n * a.out_fs;
@@ -682,6 +687,10 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
             f32x4 v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = Y[yy][xx][e] * a.wscale_inv + bv[e];
+            // an overflowed V arrives here as NaN (or +-inf); the ReLU below would store 0 for NaN
+            // and -inf, in range, so a non-finite value raises the flag before the activation:
+            // 0 v is +-0 for a number and NaN otherwise, summed here and tested once at the end
+            nonfin = __builtin_elementwise_fma(v, f32x4{0.f, 0.f, 0.f, 0.f}, nonfin);
             if (a.act == ACT_RELU) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
@@ -697,6 +706,7 @@ __global__ void __launch_bounds__(512, 1) wino_f16(W2Args a) {
     }
     __syncthreads();
   }
+  bad |= !((nonfin[0] + nonfin[1]) + (nonfin[2] + nonfin[3]) == 0.f);
   if (bad) atomicOr(a.range_flag, 1);
 }
 

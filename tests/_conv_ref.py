@@ -60,6 +60,16 @@ wino2 (csrc/wino_f16.hip): the same transforms with the three-term split of U 2^
                        + gamma(2)(1 + 2^-10) A_wino2 + c_u 2^-25 (B_wino + 2^-s X_wino)],
   B_wino = |A^T| (sum_ci |U|) |A|, X_wino = |A^T| (sum_ci |V|) |A|.
 
+  Range of the transform (emu_wino2, the plateau family).  V sums four inputs, so inputs below 65504
+  give |V| up to 4 x 65504.  The split's hi = fp16(V) is finite up to |V| < 65520 (65504 is the
+  largest fp16 number, 65520 the tie that rounds to even: to infinity); from there hi = +-inf,
+  lo = fp16(V - hi) = -+inf, and hi Uh + lo Uh + hi Ul is inf - inf: NaN in every output of the tile,
+  in every channel.  A 2x2 plateau P on a tile's inner pixels makes V[1][1] = 4 P exactly (fp32 adds
+  of equal powers-of-two multiples are exact here): P = 16376 -> 65504 (clean), 16380 -> 65520 and
+  16384 -> 65536 (overflow), 16000 -> 64000 (in range: the bound above holds unchanged, since
+  |rv| <= 2^-22 |V| + 2^-25 needs only a normal, finite hi).  The kernel must raise the range flag
+  for the overflow whatever the activation stores; a ReLU stores that NaN as 0.
+
 fp16 storage (ISL_ACT_FP16): the epilogue stores RNE(v) of a value v within the bound E of ref:
   |y - ref| <= E + half an fp16 ulp at |ref| + E   (bound_act16).
 
@@ -361,18 +371,112 @@ def emu_wino32(x, w, b, slope=None, act="none"):
     return _epilogue(acc, 1.0, b, slope, act, (n, cout, h, wd))
 
 
+GUARD_CHECKS = ("pre_and_stored", "stored_only")
+
+
+def emu_wino2(x, w, b, slope=None, act="none", terms=3, check="pre_and_stored"):
+    """csrc/wino_f16.hip in numpy, returning (y, flag).  U = G g G^T in float64, x 2^s, rounded to
+    fp32, hi = fp16(U), lo = fp16(U - hi) (pack_wino_f16).  V = B^T d B in fp32, rows then columns,
+    then split as split_dw does: hi = fp16(V) by RNE, which overflows to +-inf from |V| >= 65520, and
+    lo = fp16(V - fp32(hi)), -+inf then.  M = sum_ci of the exact products Uh Vh + Uh Vl + Ul Vh
+    (terms=1: Uh Vh alone) accumulated in fp32, Y = A^T M A in the epilogue's order, x 2^-s, + bias,
+    the activation as the kernel writes it (v > 0 ? v : 0 -- a NaN becomes 0).
+    check: where the range test sits.  "pre_and_stored": a non-finite value before the activation
+    or a stored |v| outside [0, 65504) raises the flag (the kernel); "stored_only": the stored
+    value alone (the kernel before the ReLU hole was closed: GUARD_MUTATIONS)."""
+    assert check in GUARD_CHECKS and terms in (1, 3)
+    x = np.asarray(x, np.float32)
+    n, cin, h, wd = x.shape
+    cout = w.shape[0]
+    U = np.einsum("ik,ockl,jl->ocij", _G, np.asarray(w, np.float64), _G)
+    mx = float(np.max(np.abs(U)))
+    s = 0 if mx == 0.0 else 14 - int(np.frexp(mx)[1])
+    Us = np.ldexp(U, s).astype(np.float32)
+    Uh = f16(Us)
+    Ul = f16(Us - Uh)
+    d = _tiles(x, np.float32)
+    bt = _BT.astype(np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        t = np.zeros(d.shape, np.float32)
+        for i in range(4):
+            (r0, r1) = np.nonzero(bt[i])[0]
+            t[..., i, :] = bt[i, r0] * d[..., r0, :] + bt[i, r1] * d[..., r1, :]
+        V = np.zeros(d.shape, np.float32)
+        for j in range(4):
+            (r0, r1) = np.nonzero(bt[j])[0]
+            V[..., j] = bt[j, r0] * t[..., r0] + bt[j, r1] * t[..., r1]
+        Vh = f16(V)                                      # +-inf from |V| >= 65520
+        Vl = f16(V - Vh)                                 # -+inf beside an infinite hi
+        M = np.zeros((n, cout) + d.shape[2:], np.float32)
+        for c in range(cin):
+            M += Uh[None, :, c, None, None] * Vh[:, None, c]
+            if terms == 3:
+                M += Uh[None, :, c, None, None] * Vl[:, None, c]
+                M += Ul[None, :, c, None, None] * Vh[:, None, c]
+        R0 = (M[..., 0, :] + M[..., 1, :]) + M[..., 2, :]
+        R1 = (M[..., 1, :] - M[..., 2, :]) - M[..., 3, :]
+        Y = np.empty(M.shape[:4] + (2, 2), np.float32)
+        for i, R in enumerate((R0, R1)):
+            Y[..., i, 0] = (R[..., 0] + R[..., 1]) + R[..., 2]
+            Y[..., i, 1] = (R[..., 1] - R[..., 2]) - R[..., 3]
+        pre = (_untile(Y, h, wd) * np.float32(np.ldexp(1.0, -s))).astype(np.float32)
+        pre = (pre + np.asarray(b, np.float32)[None, :, None, None]).astype(np.float32)
+        if act == "relu":
+            y = np.where(pre > 0, pre, np.float32(0))
+        elif act == "prelu":
+            y = np.where(pre >= 0, pre, pre * np.asarray(slope, np.float32)[None, :, None, None])
+        else:
+            y = pre
+        y = np.ascontiguousarray(y, np.float32)
+        flag = not bool(np.all(np.abs(y) < F16_MAX))
+        if check == "pre_and_stored":
+            flag = flag or not bool(np.all(np.isfinite(pre)))
+    return y, int(flag)
+
+
 # ---- inputs ---------------------------------------------------------------------------------
 
 FAMILIES = ("uniform", "postact", "small", "nearrange")
 NEAR_SPIKE = 16384.0
+PLATEAU_WHERE = ("interior", "row_end", "last")
 
 
-def make_x(family, shape, rng):
+def plateau_tile(shape, where):
+    """(frame, channel, ty, tx) of the Winograd tile a plateau sits in.  interior: the middle tile of
+    frame 0; row_end: the last tile of a middle tile row (W odd: the half-empty edge tile, whose
+    second inner column is outside the image); last: in the last frame, the last tile in row-major
+    order whose inner 2x2 has at least two pixels inside the image (H and W odd: the corner tile
+    holds one pixel, which alone cannot carry an overflowing V below 65504)."""
+    n, c, h, w = shape
+    th, tw = (h + 1) // 2, (w + 1) // 2
+    if where == "interior":
+        return 0, c // 2, th // 2, tw // 2
+    if where == "row_end":
+        return 0, c // 2, th // 2, tw - 1
+    if where == "last":
+        tx = tw - 2 if (h % 2 and w % 2) else tw - 1
+        return n - 1, c - 1, th - 1, tx
+    raise ValueError(where)
+
+
+def make_x(family, shape, rng, P=None, where=None):
     """The input families: uniform(-1, 1); post-activation-like (non-negative, sparse, one whole
     channel zero, signed zeros); small magnitudes (1e-5 .. 1e-3, either sign), where the fp16 lo
     halves -- below 6.1e-5 the hi halves too -- are subnormal; near the range: uniform(-1, 1) with
     one activation of 16384 at the last pixel of the last channel of the last frame, which
-    peak_weights() turns into one output near +-65504."""
+    peak_weights() turns into one output near +-65504.
+    plateau(P, where): uniform(-1, 1) with the inner 2x2 of one Winograd tile (image rows 2 ty,
+    2 ty + 1, columns 2 tx, 2 tx + 1 of one channel; plateau_tile) set so that the tile's
+    V[1][1] = d11 + d12 + d21 + d22 is 4 P exactly: P on each of the four pixels, and where the
+    image's edge clips the patch to two pixels (a half-empty edge tile), 2 P on each.  Every input
+    stays below 65504; only V = 4 P can leave the fp16 range."""
+    if family == "plateau":
+        x = rng.uniform(-1, 1, shape).astype(np.float32)
+        f, c, ty, tx = plateau_tile(shape, where)
+        patch = x[f, c, 2 * ty:2 * ty + 2, 2 * tx:2 * tx + 2]          # a view, clipped by the image
+        assert patch.size in (2, 4) and 4.0 * P / patch.size < F16_MAX
+        patch[...] = np.float32(4.0 * P / patch.size)
+        return x
     if family == "uniform":
         return rng.uniform(-1, 1, shape).astype(np.float32)
     if family == "postact":
@@ -466,3 +570,8 @@ def mutate(kind, x, w, b, slope, act, tile=128):
 
 
 MUTATIONS = ("corner_tap", "chunk_pair", "swap_channels", "tile_tail", "bias_last", "slope_neighbour")
+
+# The seventh mutation is one of the range guard, not of the values: emu_wino2's check put behind
+# the activation alone ("stored_only").  With a ReLU an overflowed V (NaN in every output of its
+# tile) is stored as 0 and the flag stays clear: the layer is wrong and says nothing.
+GUARD_MUTATIONS = ("stored_only",)

@@ -1,7 +1,10 @@
 """The references and bounds of tests/_conv_ref.py, checked on the CPU: the reference arithmetic
 alone (numpy emulations of the three-term split, the one-term mode and a float32 F(2x2, 3x3))
 stays within its bound on every input family, the 2^-25 B' term is needed where the magnitudes
-are small, and six locally wrong references all break the elementwise bound.  The figures the
+are small, and six locally wrong references all break the elementwise bound.  The range guard of
+the Winograd transform is stated here as well: an emulation of wino_f16 with its range check in
+either place flags an overflowed V with the check in front of the activation, and stores zeros
+with a clear flag under a ReLU with the check behind it (the seventh mutation).  The figures the
 module docstring and DESIGN.md quote are printed here (pytest -s)."""
 import numpy as np
 import pytest
@@ -147,6 +150,98 @@ def test_mutation_in_a_quiet_region_escapes_the_old_bar(kind):
     print("%s (quiet frame): worst |d| / bound %.3g; max |d| / max |ref| %.3g" % (kind, r, old))
     assert r > 1.0
     assert (old >= 1e-4) == (kind in QUIET_STILL_SEEN)
+
+
+# ---- the range guard of the Winograd transform ----------------------------------------------
+# V = B^T d B reaches 4 x the input: a 2x2 plateau of P on the inner pixels of one tile gives
+# V[1][1] = 4 P while every input and every true output stays below 65504.  (cin, cout, h, w):
+# odd x odd (half-empty edge tiles on both sides), the GPU test's 19 x 65, even x even.
+PLATEAU_SHAPES = [(24, 19, 9, 13), (16, 8, 19, 65), (16, 12, 8, 12)]
+PLATEAU_IDS = ["c%d-%d-%dx%d" % s for s in PLATEAU_SHAPES]
+
+
+def _plateau(shape, P, where, seed=11):
+    cin, cout, h, w = shape
+    rng = np.random.default_rng(seed)
+    x = cr.make_x("plateau", (2, cin, h, w), rng, P=P, where=where)
+    wt, b, s = cr.make_layer(cin, cout, 3, rng)
+    f, c, ty, tx = cr.plateau_tile(x.shape, where)
+    tile = (f, slice(None), slice(2 * ty, 2 * ty + 2), slice(2 * tx, 2 * tx + 2))
+    assert float(np.max(np.abs(x))) < cr.F16_MAX and float(x[f, c, 2 * ty:2 * ty + 2, 2 * tx:2 * tx + 2].sum()) == 4.0 * P
+    assert float(np.max(np.abs(cr.ref64(x, wt, b)))) < cr.F16_MAX            # only V leaves the range
+    return x, wt, b, s, tile
+
+
+@pytest.mark.parametrize("where", cr.PLATEAU_WHERE)
+@pytest.mark.parametrize("shape", PLATEAU_SHAPES, ids=PLATEAU_IDS)
+def test_transform_overflow_raises_the_flag(shape, where):
+    """P = 16384: V = 65536 splits to hi = inf, lo = -inf.  The kernel's check (before and after
+    the activation) flags it for every activation and both term counts."""
+    x, wt, b, s, tile = _plateau(shape, 16384.0, where)
+    for act in cr.ACTS:
+        for terms in (3, 1):
+            y, flag = cr.emu_wino2(x, wt, b, s, act, terms=terms)
+            assert flag == 1, (act, terms)
+            if terms == 3:                      # inf - inf: every output of the tile, every channel
+                assert np.all(y[tile] == 0) if act == "relu" else np.all(np.isnan(y[tile])), act
+            else:                               # one term: +-inf by the sign of U (NaN for a zero U)
+                assert not np.any(np.isfinite(y[tile]) & (y[tile] != 0)), act
+
+
+@pytest.mark.parametrize("kind", cr.GUARD_MUTATIONS)
+@pytest.mark.parametrize("where", cr.PLATEAU_WHERE)
+@pytest.mark.parametrize("shape", PLATEAU_SHAPES, ids=PLATEAU_IDS)
+def test_guard_mutation_escapes_with_relu(shape, where, kind):
+    """The check behind the activation alone: with a ReLU and three terms the overflowed tile is
+    stored as zeros and the flag stays clear, although the values break the bound by orders of
+    magnitude.  What tests/test_gpu_conv_layers.py::test_range_guard_transform must catch."""
+    x, wt, b, s, tile = _plateau(shape, 16384.0, where)
+    y, flag = cr.emu_wino2(x, wt, b, s, "relu", terms=3, check=kind)
+    ref = cr.ref64(x, wt, b, s, 3, "relu")
+    r, at = cr.worst(y, ref, cr.bound_wino2(x, wt, b, s, "relu"))
+    print("%s %s: flag %d, worst |d| / bound %.3g at %s, max |d| / max |ref| %.3g" % (kind, where, flag, r, at, cr.old_bar(y, ref)))
+    assert flag == 0 and np.all(y[tile] == 0) and y[tile].size > 0
+    assert r > 1.0 and np.all(np.isfinite(y))
+    assert cr.emu_wino2(x, wt, b, s, "relu", terms=3)[1] == 1          # the kernel's check sees it
+    # without the ReLU the NaN is stored, and the stored-value check alone is enough
+    for act in ("none", "prelu"):
+        assert cr.emu_wino2(x, wt, b, s, act, terms=3, check=kind)[1] == 1
+
+
+@pytest.mark.parametrize("where", cr.PLATEAU_WHERE)
+@pytest.mark.parametrize("shape", PLATEAU_SHAPES, ids=PLATEAU_IDS)
+def test_plateau_in_range_within_bound(shape, where):
+    """P = 16000: V = 64000 splits finitely.  No flag, and every element within bound_wino2."""
+    x, wt, b, s, _ = _plateau(shape, 16000.0, where)
+    for act in cr.ACTS:
+        y, flag = cr.emu_wino2(x, wt, b, s, act)
+        r, at = cr.worst(y, cr.ref64(x, wt, b, s, 3, act), cr.bound_wino2(x, wt, b, s, act))
+        print("wino2 plateau 16000 %s %s: flag %d, worst |d| / bound %.4f at %s" % (where, act, flag, r, at))
+        assert flag == 0 and r <= 1.0
+        assert cr.emu_wino2(x, wt, b, s, act, check="stored_only")[1] == 0
+
+
+@pytest.mark.parametrize("where", cr.PLATEAU_WHERE)
+def test_split_boundary(where):
+    """V = 65504 (P = 16376) is the largest fp16 number and splits exactly; V = 65520 (P = 16380)
+    is the tie that rounds to even, to infinity."""
+    with np.errstate(over="ignore"):
+        assert cr.f16(65504.0) == 65504.0 and np.isinf(cr.f16(65520.0)) and np.isfinite(cr.f16(np.nextafter(np.float32(65520.0), np.float32(0))))
+    for P, tripped in ((16376.0, 0), (16380.0, 1)):
+        x, wt, b, s, _ = _plateau(PLATEAU_SHAPES[0], P, where)
+        for act in cr.ACTS:
+            y, flag = cr.emu_wino2(x, wt, b, s, act)
+            assert flag == tripped, (P, act)
+            if not tripped:
+                assert cr.worst(y, cr.ref64(x, wt, b, s, 3, act), cr.bound_wino2(x, wt, b, s, act))[0] <= 1.0
+
+
+def test_winograd_emulation_within_bound_on_the_families():
+    """emu_wino2 on the plain input families stays within bound_wino2 with a clear flag."""
+    for family in ("uniform", "postact", "small"):
+        x, wt, b, s = _case(SHAPES[1], family)
+        y, flag = cr.emu_wino2(x, wt, b, s, "prelu")
+        assert flag == 0 and cr.worst(y, cr.ref64(x, wt, b, s, 3, "prelu"), cr.bound_wino2(x, wt, b, s, "prelu"))[0] <= 1.0
 
 
 def test_headroom_of_native_fp32():

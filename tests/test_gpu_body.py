@@ -399,6 +399,78 @@ def test_x3_range_guard_falls_back_to_fp32(w25):
     assert net.algo == "x3"
 
 
+def test_range_guard_trips_inside_a_winograd_layer(w25):
+    """The guard trips on an intermediate, not on an activation: one output channel of conv3_1
+    gets a bias of 20000, so after its ReLU that channel is a plateau of about 20000 -- in range.
+    conv3_2 runs on the Winograd kernel, whose transform V = B^T d B sums four neighbours of the
+    plateau: about 80000, which the fp16 split turns into inf - inf = NaN, and conv3_2's ReLU
+    into 0.  The flag must rise all the same, and Net.forward must fall back.
+    72 x 256 is the smallest net input that puts conv3_2 there: its 18 x 64 map has the 32 tiles
+    per row and the > 1024 pixels the launcher asks for (wino_f16_fits)."""
+    w = dict(w25)
+    b = np.array(w["conv3_1.bias"], np.float32)
+    b[7] = 20000.0
+    w["conv3_1.bias"] = b
+    x = _inputs(1, 72, 256, seed=33)
+    # torch on the CPU: no activation up to and including conv3_2 reaches 65504
+    p = cpu_ref._Params(w)
+    t = torch.from_numpy(x)
+    with torch.no_grad():
+        for name in ("conv1_1", "conv1_2", "pool", "conv2_1", "conv2_2", "pool", "conv3_1", "conv3_2"):
+            t = torch.nn.functional.max_pool2d(t, 2, 2, 0) if name == "pool" else p.conv(t, name, "relu")
+            assert float(t.abs().max()) < 65504.0, name
+            if name == "conv3_1":
+                assert float(t[0, 7].min()) > 65520.0 / 4 and tuple(t.shape[2:]) == (18, 64)   # four of them overflow V
+    net = rt.Net(rt.ISL_BODY25)
+    net.load_weights(w)
+    assert net.algo == "x3"
+    xt = torch.from_numpy(x).cuda()
+    o0 = torch.empty((1, 52, 9, 32), device="cuda")
+    o1 = torch.empty((1, 26, 9, 32), device="cuda")
+    rt.check(rt.lib().isl_net_forward(net.h, rt.ptr(xt), 1, 72, 256, rt.ptr(o0), rt.ptr(o1), rt.stream_handle()))
+    assert rt.decode_variant(dict(net.op_variants())["conv3_2"])["wino2"]
+    assert not net.range_ok()             # the raw x3 run flagged, although every activation is in range
+    assert net.range_ok()
+    paf, heat = net.forward(xt)           # guarded seam: falls back
+    rp, rh = cpu_ref.make_net_fn("body25", w)(x)
+    assert _rel(paf.cpu().numpy(), rp) < TOL and _rel(heat.cpu().numpy(), rh) < TOL
+    assert net.algo == "x3"
+
+
+@pytest.mark.parametrize("value", [70000.0, float("inf"), float("nan")], ids=["70000", "inf", "nan"])
+def test_net_input_outside_the_split_range_falls_back(net25, w25, value):
+    """The module seam takes the caller's tensor as it is: one element outside the fp16 split
+    range (too large, inf, NaN; the last pixel of the last frame) would be split to NaN by conv1_1
+    and stored as 0 by its ReLU.  The pack raises the range flag, Net.forward recomputes on the
+    fp32 kernels, and the result is torch's: equal where torch is finite, NaN where torch is NaN."""
+    x = _inputs(2, 64, 96, seed=58)
+    x[-1, -1, -1, -1] = value
+    xt = torch.from_numpy(x).cuda()
+    o0 = torch.empty((2, 52, 8, 12), device="cuda")
+    o1 = torch.empty((2, 26, 8, 12), device="cuda")
+    assert net25.algo == "x3" and net25.range_ok()
+    rt.check(rt.lib().isl_net_forward(net25.h, rt.ptr(xt), 2, 64, 96, rt.ptr(o0), rt.ptr(o1), rt.stream_handle()))
+    assert not net25.range_ok()           # raw x3 run flagged
+    assert net25.range_ok()
+    got = net25.forward(xt)               # guarded seam: falls back
+    assert net25.range_ok()               # the fallback raises nothing: the next check is clean
+    assert net25.algo == "x3"
+    ref = cpu_ref.make_net_fn("body25", w25)(x)
+    for g, r in zip(got, ref):
+        g = g.cpu().numpy()
+        fin = np.isfinite(r)
+        assert fin[0].all() and fin.any()                      # the first frame is untouched
+        assert np.array_equal(np.isnan(g), np.isnan(r))        # NaN exactly where torch has NaN
+        assert np.array_equal(g[np.isinf(r)], r[np.isinf(r)])
+        assert np.isfinite(g[fin]).all() and _rel(g[fin], r[fin]) < TOL
+        if not np.isfinite(value):
+            assert np.isnan(r[-1]).any()                       # ... and torch does have NaN here
+    # a clean input afterwards runs on the split-fp16 kernels without a flag
+    x[-1, -1, -1, -1] = 0.25
+    rt.check(rt.lib().isl_net_forward(net25.h, rt.ptr(torch.from_numpy(x).cuda()), 2, 64, 96, rt.ptr(o0), rt.ptr(o1), rt.stream_handle()))
+    assert net25.range_ok()
+
+
 @pytest.mark.parametrize("n,h,w", [(1, 184, 328), (1, 368, 656), (2, 92, 164)])
 def test_x3_splitk_small_grids(net25, w25, n, h, w):
     """K-range modes on small grids: 1 (default, canonical ranges on the <= 1024-pixel

@@ -6,7 +6,11 @@ built to reach one variant of the dispatch and is held to
   c) the same bits run to run,
   d) the last frame alone giving the bits it has in the batch, where the source promises it
      (canonical K ranges, kernels with one order at every batch size),
-  e) the variant code the case was built to reach (dispatch depends on the 256 CUs).
+  e) the variant code the case was built to reach (dispatch depends on the 256 CUs),
+  f) the range guard: a layer is within its bound or raises the flag -- at an output
+     (test_range_guard), at an intermediate while every input and output is in range
+     (test_range_guard_transform: the Winograd input transform), and on in-contract inputs of
+     large magnitude for one case per kernel family (test_flag_or_bound).
 Runs on an MI355X only (-m gpu)."""
 import contextlib
 import os
@@ -386,6 +390,127 @@ def test_range_guard(name, form):
             assert worst <= 1.0
 
 
+# ---- the range guard inside a layer: the Winograd transform ----------------------------------
+
+def by_name(name):
+    return next(c for c in CASES if c["name"] == name)
+
+
+SHARED = {}           # references shared by the parameters of one test: key -> tuple, never written to
+
+
+def shared(key, make):
+    if key not in SHARED:
+        SHARED[key] = make()
+    return SHARED[key]
+
+
+def pre_and_bound(c, x, wt, b, s):
+    """(float64 reference before the activation, three-term bound without the activation's
+    factor): every bound of _conv_ref is act_factor(slope, act) times the latter."""
+    return reference(dict(c, act="none"), "", x, wt, b, s)
+
+
+# the smallest shapes launch_wino_f16 takes (32 tiles per row, > 1024 pixels); 19 x 65 has the
+# half-empty edge tiles.  The entry has one form of this kernel: three terms (asserted below).
+TRANSFORM_CASES = ("wino2-17x63", "wino2-19x65")
+PLATEAU_OVER, PLATEAU_IN = 16384.0, 16000.0           # V = 4 P = 65536: hi = inf; 64000: a finite split
+
+
+def plateau_inputs(name, where, n, P):
+    c = by_name(name)
+
+    def make():
+        rng = np.random.default_rng(sum(map(ord, name + where)) + n)
+        x = cr.make_x("plateau", (n, c["cin"], c["h"], c["w"]), rng, P=P, where=where)
+        wt, b, s = cr.make_layer(c["cin"], c["cout"], 3, rng)
+        return (x, wt, b, s) + pre_and_bound(c, x, wt, b, s)
+    return shared(("plateau", name, where, n, P), make)
+
+
+@pytest.mark.parametrize("n", [1, 2])
+@pytest.mark.parametrize("where", cr.PLATEAU_WHERE)
+@pytest.mark.parametrize("act", cr.ACTS)
+@pytest.mark.parametrize("name", TRANSFORM_CASES)
+def test_range_guard_transform(name, act, where, n):
+    """An intermediate out of range while every input and every true output is in range: a 2x2
+    plateau on the inner pixels of one tile makes V[1][1] = 4 P.  P = 16384: V = 65536 splits to
+    hi = inf, lo = -inf, every output of the tile is NaN, and the layer must raise the flag --
+    with a ReLU too, which stores that NaN as 0.  P = 16000: V = 64000 splits finitely, no flag,
+    every element within bound_wino2."""
+    c = dict(by_name(name), act=act)
+    with pytest.raises(rt.IslError):                 # no one-term form of this kernel to cross with
+        rt.debug_conv(np.zeros((1, 8, 17, 63), np.float32), np.zeros((64, 8, 3, 3), np.float32), np.zeros(64, np.float32),
+                      f16=True, kernel="wino2")
+    for P, tripped in ((PLATEAU_OVER, True), (PLATEAU_IN, False)):
+        x, wt, b, s, pre, e = plateau_inputs(name, where, n, P)
+        ref, bound = cr.activate(pre, s, act), cr.act_factor(s, act) * e
+        assert float(np.max(np.abs(x))) < cr.F16_MAX and float(np.max(np.abs(ref))) < cr.F16_MAX   # only V overflows
+        r = launch(c, "", x, wt, b, s)
+        REACHED.add(vname(r.variant))
+        assert vname(r.variant) == c["variant"]
+        worst, at = cr.worst(r.y, ref, bound)
+        print("%s %s %s n=%d P=%g: flag %d, worst |d| / bound %.4g at %s, stray %d, unwritten %d" % (
+            name, act, where, n, P, r.range_flag, worst, at, r.stray_writes, r.unwritten))
+        assert r.range_flag == int(tripped)
+        clean(r)
+        if tripped:
+            with pytest.raises(rt.IslError, match="fp16 split range"):
+                launch(c, "", x, wt, b, s, range_error=True)
+        else:
+            assert worst <= 1.0
+
+
+# ---- flag or bound: in-contract inputs of large magnitude -----------------------------------
+
+# one case per kernel family, and what the family promises about the flag: the x3 kernels have no
+# intermediate above their inputs, so an in-range layer must not flag; the Winograd transform may
+# leave the range (V reaches 4 x the input) and then must flag; direct is the fp32 control.
+FLAG_OR_BOUND = [("union-c128", "union"), ("s-k3-c38", "plain p128"), ("g2", "ranged g2"), ("wr", "wave ranges"),
+                 ("split-c64", "split-K"), ("small7-deep", "small 7x7"), ("rgb", "rgb"), ("wino2-19x65", "wino2"),
+                 ("direct-k3", "direct")]
+
+
+def large_inputs(name):
+    """uniform(-1, 1), post-activation-like sparsity (0.6 kept, one channel zero), scaled to
+    max |x| = 0.9 x 65504; the filters scaled so that the float64 reference peaks at 0.5 x 65504
+    before the activation (a PReLU slope of 1.75 takes that to 0.875 x 65504 at most)."""
+    c = by_name(name)
+
+    def make():
+        rng = np.random.default_rng(sum(map(ord, "large" + name)))
+        shape = (c["n"], c["cin"], c["h"], c["w"])
+        x = rng.uniform(-1, 1, shape) * (rng.uniform(size=shape) < 0.6)
+        x[:, c["cin"] // 2] = 0.0
+        x = (x * (0.9 * cr.F16_MAX / np.max(np.abs(x)))).astype(np.float32)
+        wt, b, s = cr.make_layer(c["cin"], c["cout"], c["ks"], rng)
+        wt = (wt * (0.5 * cr.F16_MAX / np.max(np.abs(cr.conv64(x, wt, None))))).astype(np.float32)
+        return (x, wt, b, s) + pre_and_bound(c, x, wt, b, s)
+    return shared(("large", name), make)
+
+
+@pytest.mark.parametrize("act", ["relu", "prelu"])
+@pytest.mark.parametrize("name,family", FLAG_OR_BOUND, ids=[n for n, _ in FLAG_OR_BOUND])
+def test_flag_or_bound(name, family, act):
+    """The promise every layer test relies on: a layer either stays within its float64 bound or
+    raises the range flag -- never flag clear and wrong."""
+    c = dict(by_name(name), act=act)
+    x, wt, b, s, pre, e = large_inputs(name)
+    ref, bound = cr.activate(pre, s, act), cr.act_factor(s, act) * e
+    peak = float(np.max(np.abs(pre)))
+    assert abs(float(np.max(np.abs(x))) / (0.9 * cr.F16_MAX) - 1) < 1e-6 and abs(peak / (0.5 * cr.F16_MAX) - 1) < 1e-3
+    assert float(np.max(np.abs(ref))) < cr.F16_MAX
+    r = launch(c, "", x, wt, b, s)
+    REACHED.add(vname(r.variant))
+    assert vname(r.variant) == c["variant"]
+    worst, at = cr.worst(r.y, ref, bound)
+    print("%s (%s) %s: flag %d, worst |d| / bound %.4g at %s" % (name, family, act, r.range_flag, worst, at))
+    clean(r)
+    assert r.range_flag != 0 or worst <= 1.0
+    if c["kernel"] != "wino2":
+        assert r.range_flag == 0 and worst <= 1.0
+
+
 # ---- the coverage guard (last in the file: it reads what the tests above reached) ----------
 
 def test_coverage_of_the_dispatch():
@@ -395,6 +520,17 @@ def test_coverage_of_the_dispatch():
     where = {form_name(c["variant"], f): (c, f, {}) for c, f in RUNS}
     where.update({form_name(v[6] + ".vin", f): (vin_case(v), f, dict(vin=True)) for v in VINS for f in v[7]})
     assert set(COVERED) <= set(where)
+    # the range-guard tests above: their cases exist, are built for a listed variant (direct, the
+    # control, has no variant code), and name every kernel family once
+    for name in TRANSFORM_CASES + tuple(n for n, _ in FLAG_OR_BOUND):
+        assert by_name(name)["variant"] == "none" or by_name(name)["variant"] in COVERED, name
+    assert all(by_name(n)["kernel"] == "wino2" for n in TRANSFORM_CASES)
+    tag = {"union": ".union", "plain p128": "k3.p128.c64", "ranged g2": ".ranged.g2", "wave ranges": ".wr", "split-K": ".split",
+           "small 7x7": "k7.p64", "rgb": ".rgb", "wino2": ".w2", "direct": "none"}
+    assert [f for _, f in FLAG_OR_BOUND] == list(tag)
+    for name, family in FLAG_OR_BOUND:
+        v = by_name(name)["variant"]
+        assert v == tag[family] if family in ("plain p128", "direct") else tag[family] in v, (name, family)
     for name in COVERED:
         if name not in REACHED:
             c, f, more = where[name]
