@@ -514,6 +514,45 @@ int isl_sign_param_count(int n_features, int n_classes, int64_t* count);
 int isl_sign_classify(const float* d_params, int n_features, int window, int n_classes,
                       const float* d_windows, int batch, float* d_probs, void* stream);
 
+/* Training step of the sign classifier: the per-window loss and the gradient of the batch loss
+ * with respect to every parameter, forward and backward through time in one launch (one
+ * workgroup per window) plus one reduction launch.  DESIGN.md section 4.2k holds the definition.
+ *   model     the stack of isl_sign_classify with the same parameter layout; the three batch
+ *             normalisations use their stored moving statistics (frozen), so the gradient entries
+ *             of the 2 * n_features + 4 * 32 mean and variance slots are written as 0.
+ *   loss      l_b = logsumexp(logits_b) - logits_b[label_b]; L = (1 / batch) * sum_b w_b * l_b.
+ *             A label outside [0, n_classes) ignores the window: l_b = 0, no gradient, still
+ *             counted in batch.  d_weights NULL: every w_b is 1.
+ *   dropout   opts NULL: none.  Otherwise rates p_drop (the three Dropout layers) and p_rec (the
+ *             recurrent dropout of the four LSTM directions, one mask per direction and window
+ *             held over all steps), each in [0, 0.9], 0 = the site is off.  Draws are
+ *             counter-based: k = sm(sm(sm(seed ^ step) ^ id_b) ^ (site << 32 | index)) with the
+ *             splitmix64 finaliser sm; an element is kept iff (k >> 40) >= floor(rate * 2^24 + 0.5)
+ *             and a kept value is multiplied by the fp32 1.0f / (1.0f - rate).  d_ids NULL:
+ *             id_b = b.  A window's masks depend on neither its batch nor its place in it.
+ *   d_loss    float32 [batch], l_b.        d_grad    float32 [isl_sign_param_count], dL/dtheta.
+ *   d_workspace   isl_sign_grad_workspace bytes: one gradient slice per
+ *             workgroup (min(batch, 256) of them); workgroup j adds windows j, j + G, ... in that
+ *             order into its slice and the second launch adds the slices in index order.  No
+ *             float atomics: the same inputs give the same bits, and l_b does not depend on the
+ *             batch.
+ * ISL_E_ARG, before any device work, for: a NULL d_params, d_windows, d_labels, d_loss or
+ * d_workspace with batch > 0, a NULL d_grad, batch < 0, window outside [1, 32], n_features outside
+ * [1, 256], n_classes outside [1, 1024], a rate that is not a number in [0, 0.9], reserved not
+ * zero.  batch == 0 writes a zero gradient and returns. */
+typedef struct {
+  float p_drop, p_rec;
+  uint64_t seed, step;
+  int32_t reserved[4];
+} isl_sign_train_opts;
+
+int isl_sign_train_opts_default(isl_sign_train_opts* opts);   /* 0.2, 0.2, seed 0, step 0 */
+int isl_sign_grad_workspace(int n_features, int n_classes, int batch, int64_t* bytes);
+int isl_sign_grad(const float* d_params, int n_features, int window, int n_classes,
+                  const float* d_windows, const int32_t* d_labels, const float* d_weights,
+                  const uint64_t* d_ids, int batch, const isl_sign_train_opts* opts, float* d_loss,
+                  float* d_grad, void* d_workspace, void* stream);
+
 /* ---- augmented copies of resident frames --------------------------------- */
 
 /* One variant of a uint8 [H,W,3] frame, the reference's dataset augmentation

@@ -1,0 +1,9 @@
+def __getattr__(name):
+    # islpose.SignTrainer / islpose.SignClassifier, imported on first use
+    if name == "SignTrainer":
+        from .train import SignTrainer
+        return SignTrainer
+    if name == "SignClassifier":
+        from .translate import SignClassifier
+        return SignClassifier
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -126,7 +126,7 @@ EXPORTS = ["isl_abi_version", "isl_last_error", "isl_net_create", "isl_net_destr
            "isl_net_get_act_storage", "isl_net_act_storage_active", "isl_post_opts_default",
            "isl_body_post_opts", "isl_hand_post_opts", "isl_hand_post_crops_opts",
            "isl_net_preprocess_crops_flip", "isl_hand_post_ex", "isl_hand_post_crops_ex", "isl_augment",
-           "isl_draw",
+           "isl_draw", "isl_sign_train_opts_default", "isl_sign_grad_workspace", "isl_sign_grad",
            "isl_debug_conv3x3", "isl_debug_conv"]
 
 
@@ -168,6 +168,13 @@ class IslDrawPrim(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("p", ctypes.c_int32 * 4), ("c", ctypes.c_int32), ("s", ctypes.c_int32),
                 ("r2", ctypes.c_int32), ("color", ctypes.c_uint8 * 3), ("blend", ctypes.c_uint8),
                 ("reserved", ctypes.c_int32)]
+
+
+class IslSignTrainOpts(ctypes.Structure):
+    """isl_sign_train_opts: the rates of the three Dropout layers and of the recurrent dropout, each
+    in [0, 0.9] (0: off); seed and step of the counter-based draws; reserved zero."""
+    _fields_ = [("p_drop", ctypes.c_float), ("p_rec", ctypes.c_float), ("seed", ctypes.c_uint64),
+                ("step", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 4)]
 
 
 class IslDebugSeg(ctypes.Structure):
@@ -344,6 +351,10 @@ def lib():
     L.isl_hand_post_crops_ex.argtypes = L.isl_hand_post_crops_opts.argtypes + [pu8, vp]
     L.isl_augment.argtypes = [vp, i32, i32, i32, vp, ctypes.POINTER(IslAugItem), i32, vp]
     L.isl_draw.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(IslDrawPrim), ctypes.POINTER(i32), vp]
+    L.isl_sign_train_opts_default.argtypes = [ctypes.POINTER(IslSignTrainOpts)]
+    L.isl_sign_grad_workspace.argtypes = [i32, i32, i32, ctypes.POINTER(i64)]
+    L.isl_sign_grad.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, ctypes.POINTER(IslSignTrainOpts), vp, vp,
+                                vp, vp]
     L.isl_debug_conv3x3.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]
     L.isl_debug_conv.argtypes = [ctypes.POINTER(IslDebugConvDesc), vp, vp, vp, vp, vp, vp,
                                  ctypes.POINTER(IslDebugConvResult)]

@@ -18,6 +18,13 @@
       of a batch of 4096 windows; plus translate_stream over a 64-frame clip
       (body + hands once per frame, 45 windows classified in one launch).
 
+  TRAIN  (--config train only) SignTrainer.step (csrc/sign_train.hip) at the workload's own shape:
+      batch 256, T 20, F 156, C 167, dropout 0.2 / 0.2, Adam; HIP events, 10 warm-up calls and 30
+      timed.  Interleaved with it, the same step written as batched torch ops on the GPU (the
+      definition of DESIGN.md 4.2k vectorised over the batch, autograd, torch's own dropout
+      draws), and the forward-only isl_sign_classify at 256 windows.  Appends the result to
+      profiles/signtrain/train.jsonl.
+
 Prints one JSON line per config: frames/s, ms per step and the conv TFLOP/s of the
 step (direct-conv FLOP count, HIP events around the whole step).
 """
@@ -416,9 +423,109 @@ def c6(args):
     return res
 
 
+def torch_train_step(params, opt, x, y, p_drop, p_rec):
+    """The training step of DESIGN.md 4.2k as batched torch ops (frozen BN statistics, masks,
+    one recurrent-dropout mask per direction and window), autograd and `opt`; returns l_b."""
+    B, T, _ = x.shape
+    U = 32
+    w = params
+
+    def drop(shape, p):
+        return (torch.rand(shape, device=x.device) >= p).float() / (1.0 - p) if p > 0 else None
+
+    def bn(v, p):
+        return (v - p[2]) / torch.sqrt(p[3] + 1e-3) * p[0] + p[1]
+
+    mask = (x != 0).any(dim=2)
+
+    def lstm(inp, K, R, b, reverse, seq):
+        zx = inp @ K + b
+        h = torch.zeros(B, U, device=x.device)
+        c = torch.zeros(B, U, device=x.device)
+        rm = drop((B, U), p_rec)
+        rows = [None] * T
+        for s in range(T):
+            t = T - 1 - s if reverse else s
+            z = zx[:, t] + (h if rm is None else h * rm) @ R
+            i, f, g, o = z.split(U, dim=1)
+            c2 = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+            h2 = torch.sigmoid(o) * torch.tanh(c2)
+            mk = mask[:, t:t + 1]
+            c, h = torch.where(mk, c2, c), torch.where(mk, h2, h)
+            if seq:
+                rows[t] = torch.where(mk, h2, torch.zeros_like(h2))
+        return (torch.stack(rows, 1) if seq else None), h
+
+    def dropped(v, p):
+        m = drop(v.shape, p)
+        return v if m is None else v * m
+
+    xn = bn(x, w[0:4])
+    f1, _ = lstm(xn, w[4], w[5], w[6], False, True)
+    b1, _ = lstm(xn, w[7], w[8], w[9], True, True)
+    yseq = dropped(torch.cat([f1, b1], 2), p_drop)
+    _, hf = lstm(yseq, w[10], w[11], w[12], False, False)
+    _, hb = lstm(yseq, w[13], w[14], w[15], True, False)
+    v = torch.nn.functional.elu(torch.cat([hf, hb], 1))
+    v = torch.nn.functional.elu(dropped(bn(v @ w[16], w[17:21]), p_drop))
+    v = dropped(torch.nn.functional.elu(bn(v @ w[21], w[22:26])), p_drop)
+    loss = torch.nn.functional.cross_entropy(v @ w[26] + w[27], y, reduction="none")
+    opt.zero_grad(set_to_none=True)
+    loss.mean().backward()
+    opt.step()
+    return loss.detach()
+
+
+def train(args):
+    from islpose import translate
+    from islpose.train import SignTrainer
+    B, T, F, C = 256, 20, 156, 167
+    rng = np.random.RandomState(0)
+    xh = rng.uniform(0, 600, (B, T, F)).astype(np.float32)
+    xh[rng.rand(B, T) < 0.2] = 0
+    x = torch.from_numpy(xh).cuda()
+    y = torch.from_numpy(rng.randint(0, C, B).astype(np.int64)).cuda()
+    y32 = y.to(torch.int32)
+    tr = SignTrainer(None, F, C, p_drop=0.2, p_rec=0.2)
+    tr.calibrate_bn0(xh)
+    stat = (2, 3, 19, 20, 24, 25)
+    tw = [torch.from_numpy(a).cuda().requires_grad_(k not in stat) for k, a in enumerate(tr.weights())]
+    topt = torch.optim.Adam([p for p in tw if p.requires_grad], lr=1e-3, eps=1e-7)
+    clf = tr.classifier()
+    runs = {"hip_step": lambda: tr.step(x, y32), "torch_step": lambda: torch_train_step(tw, topt, x, y, 0.2, 0.2),
+            "classify": lambda: clf(x)}
+    warm, steps, rounds = 10, 30, 3
+    for fn in runs.values():
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in runs}
+    for _ in range(rounds):                       # interleaved: one block of timed calls each, in turn
+        for k, fn in runs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(steps // rounds):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / (steps // rounds))
+    res = {"config": "TRAIN SignTrainer.step, batch 256, T 20, F 156, C 167, dropout 0.2 / 0.2, Adam",
+           "basis": "HIP events around blocks of %d calls, %d blocks each, interleaved; %d warm-up calls"
+                    % (steps // rounds, rounds, warm)}
+    for k, v in ms.items():
+        res[k + "_us"] = [round(t * 1e3, 1) for t in v]
+        res[k + "_windows_per_s"] = round(B / (float(np.median(v)) * 1e-3), 1)
+    res["torch_over_hip"] = round(float(np.median(ms["torch_step"]) / np.median(ms["hip_step"])), 2)
+    out = os.path.join(REPO, "profiles", "signtrain")
+    os.makedirs(out, exist_ok=True)
+    with open(os.path.join(out, "train.jsonl"), "a") as f:
+        f.write(json.dumps(res) + "\n")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", choices=["c3", "c4", "c5", "c6", "frame", "hands2", "render", "all"], default="all")
+    ap.add_argument("--config", choices=["c3", "c4", "c5", "c6", "frame", "hands2", "render", "train", "all"], default="all")
     ap.add_argument("--frame-count", type=int, default=64, help="FRAME: sequential per-frame calls timed")
     ap.add_argument("--frame-repeat", type=int, default=4, help="FRAME: timed passes over the frames")
     ap.add_argument("--batch", type=int, default=16, help="C3 / C4 frames per step")
@@ -460,6 +567,9 @@ def main():
         os.environ["ISLPOSE_PRECISION"] = a.precision   # read by every net at its creation
     if a.act_storage:
         os.environ["ISLPOSE_ACT_STORAGE"] = a.act_storage
+    if a.config == "train":                          # writes its profile; not part of "all"
+        print(json.dumps(train(a)), flush=True)
+        return
     for name, fn in (("c3", c3), ("c4", c4), ("c5", c5), ("c6", c6), ("frame", frame),
                      ("hands2", hands2), ("render", render)):
         if a.config in (name, "all"):
