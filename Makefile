@@ -1,5 +1,6 @@
 # Build libislpose.so (HIP, gfx950) in-tree, and the oracle's reference build helpers.
 HIPCC    ?= /opt/rocm/bin/hipcc
+HOSTCXX  ?= /opt/rocm/llvm/bin/clang++
 ARCH     ?= gfx950
 PKG      := isl-signlanguage-translation_amd
 CSRC     := $(PKG)/csrc
@@ -8,7 +9,7 @@ OUT      := $(PKG)/islpose/libislpose.so
 # operation order bit-for-bit, which forbids fused multiply-adds.
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Iinclude -I$(CSRC) \
             -Wall -Wno-unused-function -Wno-unused-variable -Wno-unused-lambda-capture
-SRCS     := $(CSRC)/conv.hip $(CSRC)/conv_x3.hip $(CSRC)/conv_c12.hip $(CSRC)/wino_f16.hip $(CSRC)/wino.hip $(CSRC)/ops.hip $(CSRC)/post.hip $(CSRC)/sign.hip $(CSRC)/sign_train.hip $(CSRC)/augment.hip $(CSRC)/draw.hip $(CSRC)/runtime.cpp
+SRCS     := $(CSRC)/conv.hip $(CSRC)/conv_x3.hip $(CSRC)/conv_c12.hip $(CSRC)/wino_f16.hip $(CSRC)/wino.hip $(CSRC)/ops.hip $(CSRC)/post.hip $(CSRC)/sign.hip $(CSRC)/sign_train.hip $(CSRC)/augment.hip $(CSRC)/draw.hip $(CSRC)/pack.cpp $(CSRC)/runtime.cpp
 OBJS     := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 # development objects (tools/convbench): the product sources plus the rejected split-fp16
 # Winograd kernel and the s_memtime stamp variant, compiled with -DISLPOSE_DEV
@@ -17,14 +18,14 @@ DEV_OBJS := $(patsubst $(CSRC)/%,build_dev/%.o,$(DEV_SRCS))
 
 all: $(OUT)
 
-build/%.o: $(CSRC)/% $(CSRC)/internal.h $(CSRC)/sign_common.h include/islpose.h
+build/%.o: $(CSRC)/% $(CSRC)/internal.h $(CSRC)/pack.h $(CSRC)/sign_common.h include/islpose.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 $(OUT): $(OBJS)
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,-z,defs -o $@ $(OBJS)
 
-build_dev/%.o: $(CSRC)/% $(CSRC)/internal.h $(CSRC)/sign_common.h include/islpose.h
+build_dev/%.o: $(CSRC)/% $(CSRC)/internal.h $(CSRC)/pack.h $(CSRC)/sign_common.h include/islpose.h
 	@mkdir -p build_dev
 	$(HIPCC) $(HIPFLAGS) -DISLPOSE_DEV -x hip -c $< -o $@
 
@@ -40,3 +41,7 @@ clean:
 # development microbenchmark of the conv kernels (not part of the library)
 tools/convbench: tools/convbench.cpp $(DEV_OBJS)
 	$(HIPCC) $(HIPFLAGS) -DISLPOSE_DEV -x hip tools/convbench.cpp -x none $(DEV_OBJS) -o $@
+
+# digests of the weight packs on the CPU (tests/test_pack.py): host compiler only, no device
+tools/pack_digest: tools/pack_digest.cpp $(CSRC)/pack.cpp $(CSRC)/pack.h
+	$(HOSTCXX) -O2 -std=c++17 -ffp-contract=off -Wall -I$(CSRC) tools/pack_digest.cpp $(CSRC)/pack.cpp -o $@

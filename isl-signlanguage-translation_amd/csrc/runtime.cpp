@@ -1,5 +1,5 @@
-// libislpose runtime: network graphs, weight packing, activation arena and the
-// C ABI of include/islpose.h.
+// libislpose runtime: network graphs, weight upload (the packs are built in pack.cpp),
+// activation arena and the C ABI of include/islpose.h.
 //
 // The three networks of src/model.py are rebuilt here as static graphs over
 // padded buffers in 8-channel chunks.  Every torch.cat of the reference (model.py:177, 190,
@@ -21,6 +21,7 @@
 
 #include "internal.h"
 #include "islpose.h"
+#include "pack.h"
 
 namespace isl {
 
@@ -45,50 +46,29 @@ static int fail(int code, const std::string& msg) {
 // layer tables (model.py)
 // ---------------------------------------------------------------------------
 
-struct Seg {
-  int logical, phys, len;  // logical input channels [logical, logical+len) live at physical offset phys
+static_assert(PACK_ACT_PRELU == ACT_PRELU && PACK_WINO_X3_BCO == WINO_X3_BCO, "pack.h mirrors internal.h");
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
 };
 
-struct ConvLayer {
+// A layer: its host view (pack.h) and its device buffers, all owned here and freed in
+// isl_net_destroy
+struct ConvLayer : PackLayer {
   std::string name, prelu;
-  int cin = 0, cout = 0, k = 0, act = ACT_RELU;
-  std::vector<float> w, b, s;
   bool has_w = false, has_b = false, has_s = false;
-  std::vector<Seg> cmap;
-  int cin_phys = 0, bco = 0;
-  bool x3_wide = false;          // 1x1 layer with a second split-fp16 packing for 256-channel tiles
-  int wbco = 0;                  // Winograd tile (3x3 layers), 0 = direct only
-  float *d_w = nullptr, *d_b = nullptr, *d_s = nullptr;
-  float* d_wu = nullptr;         // Winograd-transformed filters
-  void* d_wx3 = nullptr;         // split-fp16 filters (conv_x3.hip), tiles of bco channels
-  void* d_wx3w = nullptr;        // the same for 256-channel tiles (x3_wide layers; per launch, x3_wide1)
-  void* d_wrgb = nullptr;        // conv1_1: filters with K packed as the 27 real (ky, kx, c) values
-  float x3_inv = 1.f;            // 2^-s of the split weights
-  void* d_wux3 = nullptr;        // split-fp16 Winograd filters (wino_x3.hip), 3x3 only
-  float wx3_inv = 1.f;
-  void* d_ww = nullptr;          // split-fp16 Winograd filters of wino_f16.hip (3x3, cout % 64 == 0)
-  float ww_inv = 1.f;            // their 2^-s
-  // the fused 1x1 pair (conv_x3 VAR 16): fuse6 marks the first layer (Mconv6), packed once
-  // more for one tile of all its channels (d_wx3f, when bco < cout); fuse7 the second, packed
-  // in the fused K order (d_wx3f7, pack_x3_f7)
-  bool fuse6 = false, fuse7 = false;
-  void* d_wx3f = nullptr;
-  void* d_wx3f7 = nullptr;
-  // ... and for the pair's two-launch form on small grids: Mconv6 writes its channels in the
-  // fused K order (rows, bias and slopes permuted: d_wx3p, d_bp, d_sp), Mconv7 reads them
-  // through that channel map (d_wx3p)
-  void* d_wx3p = nullptr;
-  float *d_bp = nullptr, *d_sp = nullptr;
-  // ISL_PREC_FP16: the hi halves alone of d_wx3 / d_wx3w / d_wrgb (pack_hi_only: the same 2^s,
-  // the same layouts without [hi|lo]), built when the mode is first used (upload_hi_packs)
-  void* d_hx3 = nullptr;
-  void* d_hx3w = nullptr;
-  void* d_hrgb = nullptr;
-  // ... and of the fusable pair's packs d_wx3f / d_wx3f7 / d_wx3p (the one-term fused launch and
-  // its permuted two-launch form), built and invalidated with the others
-  void* d_hx3f = nullptr;
-  void* d_hx3f7 = nullptr;
-  void* d_hx3p = nullptr;
+  // the packs the layer owns (owns_pack), [kind][full | hi-only].  The hi-only forms are
+  // ISL_PREC_FP16's: the same 2^s, the same layouts without [hi|lo], built when the mode is
+  // first used (upload_hi_packs)
+  DevBuf dev[PK_COUNT][2];
+  float inv[PK_COUNT];           // 2^-s of the split packs
+  DevBuf par[PB_COUNT];          // bias and slopes, padded (build_param)
+  ConvLayer() { std::fill(inv, inv + PK_COUNT, 1.f); }
+  const void* pack(int kind, bool h16 = false) const { return dev[kind][h16].p; }
+  const float* param(int which) const { return (const float*)par[which].p; }
+  // Mconv6 of the fused pair: one tile of all its channels, which is PK_X3 where bco == cout
+  int pair6_kind() const { return owns_pack(*this, PK_X3F) ? PK_X3F : PK_X3; }
 };
 
 static ConvLayer mk(const std::string& name, int cin, int cout, int k, int act, const std::string& prelu = "") {
@@ -494,208 +474,6 @@ static void build_hand(isl_net* net) {
   net->n_out = 1;
 }
 
-// Repack OIHW weights into [co_tile][chunk][ky][kx][plane(2)][BCO][4] (see conv.hip).
-static std::vector<float> pack_weights(const ConvLayer& c) {
-  const int ks = c.k, bco = c.bco, chunks = c.cin_phys / 8;
-  const int co_tiles = (c.cout + bco - 1) / bco;
-  std::vector<int> p2l(c.cin_phys, -1);
-  for (const Seg& s : c.cmap)
-    for (int i = 0; i < s.len; ++i) p2l[s.phys + i] = s.logical + i;
-  std::vector<float> out((size_t)co_tiles * chunks * ks * ks * 2 * bco * 4, 0.f);
-  size_t idx = 0;
-  for (int ct = 0; ct < co_tiles; ++ct)
-    for (int ch = 0; ch < chunks; ++ch)
-      for (int ky = 0; ky < ks; ++ky)
-        for (int kx = 0; kx < ks; ++kx)
-          for (int pl = 0; pl < 2; ++pl)
-            for (int i = 0; i < bco; ++i)
-              for (int e = 0; e < 4; ++e, ++idx) {
-                const int co = ct * bco + i, lci = p2l[ch * 8 + pl * 4 + e];
-                if (co < c.cout && lci >= 0) out[idx] = c.w[(((size_t)co * c.cin + lci) * ks + ky) * ks + kx];
-              }
-  return out;
-}
-
-// U = G g G^T of every (co, physical ci) 3x3 filter, in double, rounded once to
-// fp32; layout [co_tile][chunk][xi = 4*row + col][plane][BCO][4] (wino.hip).
-static std::vector<float> pack_wino(const ConvLayer& c) {
-  const int bco = c.wbco, chunks = c.cin_phys / 8, co_tiles = c.cout / bco;
-  std::vector<int> p2l(c.cin_phys, -1);
-  for (const Seg& s : c.cmap)
-    for (int i = 0; i < s.len; ++i) p2l[s.phys + i] = s.logical + i;
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  std::vector<float> out((size_t)co_tiles * chunks * 16 * 2 * bco * 4, 0.f);
-  for (int co = 0; co < c.cout; ++co)
-    for (int pc = 0; pc < c.cin_phys; ++pc) {
-      const int lci = p2l[pc];
-      if (lci < 0) continue;
-      const float* g = &c.w[((size_t)co * c.cin + lci) * 9];
-      double t[4][3];
-      for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 3; ++j) t[i][j] = G[i][0] * g[0 * 3 + j] + G[i][1] * g[1 * 3 + j] + G[i][2] * g[2 * 3 + j];
-      const int ct = co / bco, i_co = co % bco, ch = pc / 8, pl = (pc % 8) / 4, e = pc % 4;
-      for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-          const double u = t[i][0] * G[j][0] + t[i][1] * G[j][1] + t[i][2] * G[j][2];
-          const int xi = 4 * i + j;
-          out[((((size_t)ct * chunks + ch) * 16 + xi) * 2 + pl) * bco * 4 + (size_t)i_co * 4 + e] = (float)u;
-        }
-    }
-  return out;
-}
-
-// Split-fp16 filters for conv_x3.hip: w * 2^s = hi + lo (both fp16, round to
-// nearest), 2^s chosen per layer so that max|w| * 2^s lies in [2^13, 2^14);
-// layout [co_tile][chunk pair][ky][kx][hi|lo][h][BCO][8], h = chunk of the pair.
-static std::vector<_Float16> pack_x3(const ConvLayer& c, int bco, float* inv_scale) {
-  const int ks = c.k, chunks = c.cin_phys / 8, pairs = (chunks + 1) / 2;
-  const int co_tiles = (c.cout + bco - 1) / bco;
-  std::vector<int> p2l(pairs * 16, -1);
-  for (const Seg& s : c.cmap)
-    for (int i = 0; i < s.len; ++i) p2l[s.phys + i] = s.logical + i;
-  float mx = 0.f;
-  for (float v : c.w) mx = std::max(mx, std::fabs(v));
-  int e = 0;
-  if (mx > 0.f) {
-    std::frexp(mx, &e);            // mx = f * 2^e, f in [0.5, 1)
-    e = 14 - e;                    // mx * 2^e in [2^13, 2^14)
-  }
-  const float scale = std::ldexp(1.f, e);
-  *inv_scale = std::ldexp(1.f, -e);
-  std::vector<_Float16> out((size_t)co_tiles * pairs * ks * ks * 2 * 2 * bco * 8, (_Float16)0.f);
-  for (int ct = 0; ct < co_tiles; ++ct)
-    for (int pr = 0; pr < pairs; ++pr)
-      for (int ky = 0; ky < ks; ++ky)
-        for (int kx = 0; kx < ks; ++kx)
-          for (int h = 0; h < 2; ++h)
-            for (int i = 0; i < bco; ++i)
-              for (int j = 0; j < 8; ++j) {
-                const int co = ct * bco + i, lci = p2l[pr * 16 + h * 8 + j];
-                if (co >= c.cout || lci < 0) continue;
-                const float w = c.w[(((size_t)co * c.cin + lci) * ks + ky) * ks + kx] * scale;
-                const _Float16 hi = (_Float16)w;
-                const _Float16 lo = (_Float16)(w - (float)hi);
-                const size_t base = ((((size_t)(ct * pairs + pr) * ks + ky) * ks + kx) * 2) * 2 * bco;
-                out[((base + 0 * 2 * bco) + (size_t)h * bco + i) * 8 + j] = hi;
-                out[((base + 1 * 2 * bco) + (size_t)h * bco + i) * 8 + j] = lo;
-              }
-  return out;
-}
-
-// Split-fp16 Winograd filters for wino_f16.hip: U = G g G^T per (co, physical ci) in double,
-// scaled by a per-layer 2^s (max|U| * 2^s in [2^13, 2^14), as pack_x3), rounded to fp32 and
-// split hi + lo; layout [co_block 64][pair][xi 16][co tile i 2][hi|lo][h][32][8] -- one wave's
-// filters of a K step are 4 contiguous 1 KiB pieces (i, hi|lo), lane = h * 32 + co.
-static std::vector<_Float16> pack_wino_f16(const ConvLayer& c, float* inv_scale) {
-  const int chunks = c.cin_phys / 8, pairs = (chunks + 1) / 2, cob = c.cout / 64;
-  std::vector<int> p2l(pairs * 16, -1);
-  for (const Seg& sg : c.cmap)
-    for (int i = 0; i < sg.len; ++i) p2l[sg.phys + i] = sg.logical + i;
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  std::vector<double> U((size_t)c.cout * pairs * 16 * 16, 0.0);   // [co][pc][xi]
-  double mx = 0.0;
-  for (int co = 0; co < c.cout; ++co)
-    for (int pc = 0; pc < pairs * 16; ++pc) {
-      const int lci = p2l[pc];
-      if (lci < 0) continue;
-      const float* g = &c.w[((size_t)co * c.cin + lci) * 9];
-      double t[4][3];
-      for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 3; ++j) t[i][j] = G[i][0] * g[0 * 3 + j] + G[i][1] * g[1 * 3 + j] + G[i][2] * g[2 * 3 + j];
-      for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-          const double u = t[i][0] * G[j][0] + t[i][1] * G[j][1] + t[i][2] * G[j][2];
-          U[((size_t)co * pairs * 16 + pc) * 16 + 4 * i + j] = u;
-          mx = std::max(mx, std::fabs(u));
-        }
-    }
-  int e = 0;
-  if (mx > 0.0) {
-    std::frexp(mx, &e);
-    e = 14 - e;
-  }
-  const double scale = std::ldexp(1.0, e);
-  *inv_scale = std::ldexp(1.f, -e);
-  std::vector<_Float16> out((size_t)cob * pairs * 16 * 2 * 2 * 2 * 32 * 8, (_Float16)0.f);
-  for (int co = 0; co < c.cout; ++co)
-    for (int pc = 0; pc < pairs * 16; ++pc) {
-      if (p2l[pc] < 0) continue;
-      const int cb = co / 64, i = (co % 64) / 32, r = co % 32, pr = pc / 16, h = (pc % 16) / 8, k = pc % 8;
-      for (int xi = 0; xi < 16; ++xi) {
-        const float w = (float)(U[((size_t)co * pairs * 16 + pc) * 16 + xi] * scale);
-        const _Float16 hi = (_Float16)w;
-        const _Float16 lo = (_Float16)(w - (float)hi);
-        const size_t base = ((((size_t)cb * pairs + pr) * 16 + xi) * 2 + i) * 2;
-        out[(((base + 0) * 2 + h) * 32 + r) * 8 + k] = hi;
-        out[(((base + 1) * 2 + h) * 32 + r) * 8 + k] = lo;
-      }
-    }
-  return out;
-}
-
-// conv1_1 filters for conv_x3_rgb: K = 9 ky + 3 kx + c (27 real, padded to 32),
-// k = 16 kk + 8 h + j, layout [kk][hi|lo][h][64][8]; the same 2^s as pack_x3.
-static bool rgb_layer(const ConvLayer& c) {
-  return c.k == 3 && c.cin == 3 && c.cin_phys == 8 && c.cout <= 64 && c.cmap.size() == 1 && c.cmap[0].phys == 0 &&
-         c.cmap[0].logical == 0 && c.cmap[0].len == 3;
-}
-
-static std::vector<_Float16> pack_x3_rgb(const ConvLayer& c) {
-  float mx = 0.f;
-  for (float v : c.w) mx = std::max(mx, std::fabs(v));
-  int e = 0;
-  if (mx > 0.f) {
-    std::frexp(mx, &e);
-    e = 14 - e;
-  }
-  const float scale = std::ldexp(1.f, e);
-  std::vector<_Float16> out((size_t)2 * 2 * 2 * 64 * 8, (_Float16)0.f);
-  for (int k = 0; k < 27; ++k) {
-    const int ky = k / 9, kx = (k % 9) / 3, ci = k % 3, kk = k / 16, h = (k % 16) / 8, j = k % 8;
-    for (int co = 0; co < c.cout; ++co) {
-      const float w = c.w[(((size_t)co * 3 + ci) * 3 + ky) * 3 + kx] * scale;
-      const _Float16 hi = (_Float16)w;
-      out[((((size_t)kk * 2 + 0) * 2 + h) * 64 + co) * 8 + j] = hi;
-      out[((((size_t)kk * 2 + 1) * 2 + h) * 64 + co) * 8 + j] = (_Float16)(w - (float)hi);
-    }
-  }
-  return out;
-}
-
-// Mconv7 of a fused 1x1 pair (conv_x3 VAR 16): the K order of Mconv6's accumulator
-// registers.  K block kb = 2 g + q covers Mconv6 channels [32 g, 32 g + 32) half q; its slot j
-// of lane half h is register 8 q + j of that 32-row D tile, i.e. channel
-// 32 g + 16 q + 8 (j >> 2) + 4 h + (j & 3).  Layout [row tile t][kb][hi|lo][h][32][8], the same
-// 2^s as pack_x3 (max|w| * 2^s in [2^13, 2^14)).
-static std::vector<_Float16> pack_x3_f7(const ConvLayer& c, float* inv_scale) {
-  float mx = 0.f;
-  for (float v : c.w) mx = std::max(mx, std::fabs(v));
-  int e = 0;
-  if (mx > 0.f) {
-    std::frexp(mx, &e);
-    e = 14 - e;
-  }
-  const float scale = std::ldexp(1.f, e);
-  *inv_scale = std::ldexp(1.f, -e);
-  const int nt = (c.cout + 31) / 32, kbs = c.cin / 16;
-  std::vector<_Float16> out((size_t)nt * kbs * 2 * 2 * 32 * 8, (_Float16)0.f);
-  for (int t = 0; t < nt; ++t)
-    for (int kb = 0; kb < kbs; ++kb)
-      for (int h = 0; h < 2; ++h)
-        for (int row = 0; row < 32; ++row)
-          for (int j = 0; j < 8; ++j) {
-            const int co = 32 * t + row;
-            if (co >= c.cout) continue;
-            const int ch = 32 * (kb >> 1) + 16 * (kb & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
-            const float w = c.w[(size_t)co * c.cin + ch] * scale;
-            const _Float16 hi = (_Float16)w;
-            const size_t base = ((size_t)(t * kbs + kb) * 2) * 64;
-            out[(base + h * 32 + row) * 8 + j] = hi;
-            out[(base + 64 + h * 32 + row) * 8 + j] = (_Float16)(w - (float)hi);
-          }
-  return out;
-}
-
 // Fusable 1x1 pairs (conv_x3 VAR 16): op k and op k + 1 both 1x1 convs, op k + 1 reading the
 // whole output of op k (offset 0, identity channel map) from a buffer no other op reads before
 // it is written again and that is no net output, shapes with a fused variant (x3_fused67_fits).  body_25's six
@@ -739,34 +517,6 @@ static void plan_fuse67(isl_net* net) {
   }
 }
 
-// Mconv6 output channel order of a fusable pair's two-launch form: physical channel
-// 16 p + 8 h + j (chunk h of pair p, element j) holds the channel that sits in slot j of lane
-// half h of the fused kernel's K block p (pack_x3_f7): 32 g + 16 q + 8 (j >> 2) + 4 h + (j & 3),
-// p = 2 g + q.  Mconv7 then stages exactly the fused kernel's B fragments.
-static int f7_logical(int phys) {
-  const int p = phys >> 4, h = (phys >> 3) & 1, j = phys & 7, g = p >> 1, q = p & 1;
-  return 32 * g + 16 * q + 8 * (j >> 2) + 4 * h + (j & 3);
-}
-
-// The permuted copies of a fusable pair's layers (two-launch form): Mconv6 with its output
-// rows (weights, bias, slopes) in f7_logical order, Mconv7 with the matching channel map
-static ConvLayer f7_permuted(const ConvLayer& c) {
-  ConvLayer p = c;
-  if (c.fuse6) {
-    const size_t per = (size_t)c.cin * c.k * c.k;
-    for (int ph = 0; ph < c.cout; ++ph) {
-      const int lg = f7_logical(ph);
-      std::copy(c.w.begin() + lg * per, c.w.begin() + (lg + 1) * per, p.w.begin() + ph * per);
-      p.b[ph] = c.b[lg];
-      if (c.act == ACT_PRELU) p.s[ph] = c.s[lg];
-    }
-  } else {
-    p.cmap.clear();
-    for (int ph = 0; ph < c.cin; ++ph) p.cmap.push_back({f7_logical(ph), ph, 1});
-  }
-  return p;
-}
-
 // ISLPOSE_X3_FUSE67: 0 the pairs as two plain launches (natural channel order; A/B), 2 always
 // fused, 3 always the permuted two launches (tests), default by grid (x3_fused67_grid); read
 // per run.  ISL_PREC_FP16 (h16): the one-term forms of both exist, but the fused K order of Mconv7
@@ -791,110 +541,41 @@ static int fuse67_form(const isl_net* net, const std::vector<Act>& act, size_t k
   return 1;
 }
 
-#ifdef ISLPOSE_DEV
-// Split-fp16 Winograd filters for wino_x3.hip: U = G g G^T (double) per (co,
-// physical ci), scaled by a per-layer 2^s (max|U| * 2^s in [2^13, 2^14)), split
-// hi + lo; layout [co_tile][pair][xi][hi|lo][h][64][8], h = chunk of the pair.
-static std::vector<_Float16> pack_wino_x3(const ConvLayer& c, float* inv_scale) {
-  constexpr int BCO = WINO_X3_BCO;
-  const int chunks = c.cin_phys / 8, pairs = (chunks + 1) / 2, co_tiles = (c.cout + BCO - 1) / BCO;
-  std::vector<int> p2l(pairs * 16, -1);
-  for (const Seg& sg : c.cmap)
-    for (int i = 0; i < sg.len; ++i) p2l[sg.phys + i] = sg.logical + i;
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  std::vector<double> U((size_t)c.cout * pairs * 16 * 16, 0.0);   // [co][pc][xi]
-  double mx = 0.0;
-  for (int co = 0; co < c.cout; ++co)
-    for (int pc = 0; pc < pairs * 16; ++pc) {
-      const int lci = p2l[pc];
-      if (lci < 0) continue;
-      const float* g = &c.w[((size_t)co * c.cin + lci) * 9];
-      double t[4][3];
-      for (int i = 0; i < 4; ++i)
-        for (int jj = 0; jj < 3; ++jj) t[i][jj] = G[i][0] * g[0 * 3 + jj] + G[i][1] * g[1 * 3 + jj] + G[i][2] * g[2 * 3 + jj];
-      for (int i = 0; i < 4; ++i)
-        for (int jj = 0; jj < 4; ++jj) {
-          const double u = t[i][0] * G[jj][0] + t[i][1] * G[jj][1] + t[i][2] * G[jj][2];
-          U[((size_t)co * pairs * 16 + pc) * 16 + 4 * i + jj] = u;
-          mx = std::max(mx, std::fabs(u));
-        }
-    }
-  int e = 0;
-  if (mx > 0.0) {
-    std::frexp(mx, &e);
-    e = 14 - e;
-  }
-  const double scale = std::ldexp(1.0, e);
-  *inv_scale = std::ldexp(1.f, -e);
-  std::vector<_Float16> out((size_t)co_tiles * pairs * 16 * 2 * 2 * BCO * 8, (_Float16)0.f);
-  for (int co = 0; co < c.cout; ++co)
-    for (int pc = 0; pc < pairs * 16; ++pc) {
-      if (p2l[pc] < 0) continue;
-      const int ct = co / BCO, i_co = co % BCO, pr = pc / 16, h = (pc % 16) / 8, k = pc % 8;
-      for (int xi = 0; xi < 16; ++xi) {
-        const float w = (float)(U[((size_t)co * pairs * 16 + pc) * 16 + xi] * scale);
-        const _Float16 hi = (_Float16)w;
-        const _Float16 lo = (_Float16)(w - (float)hi);
-        const size_t base = (((size_t)ct * pairs + pr) * 16 + xi) * 2;
-        out[(((base + 0) * 2 + h) * BCO + i_co) * 8 + k] = hi;
-        out[(((base + 1) * 2 + h) * BCO + i_co) * 8 + k] = lo;
-      }
-    }
-  return out;
-}
-#endif
-
-// The hi halves of a split pack whose [hi|lo] dimension has `group` fp16 values per plane
-// (pack_x3: 2 * bco * 8, pack_x3_rgb: 2 * 64 * 8): the planes [.. ][hi] in order, i.e. the same
-// layout without that dimension and the same 2^s -- the filters rounded once to fp16 (RNE)
-static std::vector<_Float16> pack_hi_only(const std::vector<_Float16>& split, size_t group) {
-  std::vector<_Float16> out(split.size() / 2);
-  for (size_t g = 0; g < out.size() / group; ++g)
-    std::copy(split.begin() + 2 * g * group, split.begin() + (2 * g + 1) * group, out.begin() + g * group);
-  return out;
-}
-
 static void drop_all_graphs(isl_net* net);
+
+// Every weight buffer goes up through here: allocated on first use, the same size ever after
+// (a layer's shape is fixed), copied by a blocking copy
+static int upload(DevBuf& d, const void* host, size_t bytes) {
+  if (!d.p) {
+    HIP_OK(hipMalloc(&d.p, bytes));
+    d.bytes = bytes;
+  }
+  if (d.bytes != bytes) return fail(ISL_E_STATE, "weight upload: buffer size changed");
+  HIP_OK(hipMemcpy(d.p, host, bytes, hipMemcpyHostToDevice));
+  return ISL_OK;
+}
+
+// Build and upload the packs every layer owns (owns_pack), full or hi-only.  A layer has one
+// 2^s, PK_X3's: the packs the kernels read beside it must reproduce it.
+static int upload_packs(isl_net* net, bool hi) {
+  for (ConvLayer& c : net->layers)
+    for (int kind = 0; kind < PK_COUNT; ++kind) {
+      if (!owns_pack(c, kind) || (hi && !pack_has_hi(kind))) continue;
+      float inv = 1.f;
+      const HostPack hp = build_pack(c, kind, hi, &inv);
+      const char* same = kind == PK_X3F7 ? "Mconv7 scale mismatch" : kind == PK_X3P ? "permuted scale mismatch"
+                         : kind == PK_X3 && hi ? "scale mismatch" : nullptr;
+      if (same && inv != c.inv[PK_X3]) return fail(ISL_E_STATE, std::string(hi ? "hi-only pack: " : "fused pair: ") + same);
+      if (!hi) c.inv[kind] = inv;
+      if (const int rc = upload(c.dev[kind][hi], hp.data(), hp.bytes())) return rc;
+    }
+  return ISL_OK;
+}
 
 // ISL_PREC_FP16's filters: built when a run first needs them after a weight upload (at the
 // upload itself when the mode is already selected), kept across precision switches
 static int upload_hi_packs(isl_net* net) {
-  for (ConvLayer& c : net->layers) {
-    float inv = 1.f;
-    {
-      std::vector<_Float16> hp = pack_hi_only(pack_x3(c, c.bco, &inv), (size_t)2 * c.bco * 8);
-      if (inv != c.x3_inv) return fail(ISL_E_STATE, "hi-only pack: scale mismatch");
-      if (!c.d_hx3) HIP_OK(hipMalloc(&c.d_hx3, hp.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_hx3, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-    if (rgb_layer(c)) {
-      std::vector<_Float16> hp = pack_hi_only(pack_x3_rgb(c), (size_t)2 * 64 * 8);
-      if (!c.d_hrgb) HIP_OK(hipMalloc(&c.d_hrgb, hp.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_hrgb, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-    if (c.x3_wide) {
-      std::vector<_Float16> hp = pack_hi_only(pack_x3(c, 256, &inv), (size_t)2 * 256 * 8);
-      if (!c.d_hx3w) HIP_OK(hipMalloc(&c.d_hx3w, hp.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_hx3w, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-    if (c.fuse6 && c.bco != c.cout) {   // one tile of all channels for the fused pair
-      std::vector<_Float16> hp = pack_hi_only(pack_x3(c, c.cout, &inv), (size_t)2 * c.cout * 8);
-      if (!c.d_hx3f) HIP_OK(hipMalloc(&c.d_hx3f, hp.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_hx3f, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-    if (c.fuse7) {                      // pack_x3_f7: [t][kb][hi|lo][h][32][8]
-      std::vector<_Float16> hp = pack_hi_only(pack_x3_f7(c, &inv), (size_t)2 * 32 * 8);
-      if (inv != c.x3_inv) return fail(ISL_E_STATE, "hi-only pack: Mconv7 scale mismatch");
-      if (!c.d_hx3f7) HIP_OK(hipMalloc(&c.d_hx3f7, hp.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_hx3f7, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-    if (c.fuse6 || c.fuse7) {           // the pair's permuted two-launch form
-      std::vector<_Float16> hp = pack_hi_only(pack_x3(f7_permuted(c), c.bco, &inv), (size_t)2 * c.bco * 8);
-      if (inv != c.x3_inv) return fail(ISL_E_STATE, "hi-only pack: permuted scale mismatch");
-      if (!c.d_hx3p) HIP_OK(hipMalloc(&c.d_hx3p, hp.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_hx3p, hp.data(), hp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-  }
+  if (const int rc = upload_packs(net, true)) return rc;
   net->packed_hi = true;
   return ISL_OK;
 }
@@ -905,82 +586,13 @@ static int upload_params(isl_net* net) {
   for (ConvLayer& c : net->layers) {
     if (!c.has_w || !c.has_b || (c.act == ACT_PRELU && !c.has_s))
       return fail(ISL_E_STATE, "parameter missing for layer " + c.name);
-    std::vector<float> wp = pack_weights(c);
-    // bias / slopes padded for every tile width (c.bco; 256 for x3_wide layers)
-    const int wpad = std::max((c.cout + c.bco - 1) / c.bco * c.bco, (c.cout + 255) / 256 * 256);
-    std::vector<float> bp((size_t)wpad, 0.f), sp((size_t)wpad, 0.f);
-    std::copy(c.b.begin(), c.b.end(), bp.begin());
-    if (c.act == ACT_PRELU) std::copy(c.s.begin(), c.s.end(), sp.begin());
-    if (!c.d_w) HIP_OK(hipMalloc(&c.d_w, wp.size() * sizeof(float)));
-    if (!c.d_b) HIP_OK(hipMalloc(&c.d_b, bp.size() * sizeof(float)));
-    if (!c.d_s) HIP_OK(hipMalloc(&c.d_s, sp.size() * sizeof(float)));
-    HIP_OK(hipMemcpy(c.d_w, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(c.d_b, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(c.d_s, sp.data(), sp.size() * sizeof(float), hipMemcpyHostToDevice));
-    {
-      std::vector<_Float16> xp = pack_x3(c, c.bco, &c.x3_inv);
-      if (!c.d_wx3) HIP_OK(hipMalloc(&c.d_wx3, xp.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_wx3, xp.data(), xp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-    if (rgb_layer(c)) {
-      std::vector<_Float16> rp = pack_x3_rgb(c);
-      if (!c.d_wrgb) HIP_OK(hipMalloc(&c.d_wrgb, rp.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_wrgb, rp.data(), rp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-    if (c.fuse6 && c.bco != c.cout) {   // one tile of all channels for the fused pair
-      float inv = 1.f;
-      std::vector<_Float16> xp = pack_x3(c, c.cout, &inv);
-      if (!c.d_wx3f) HIP_OK(hipMalloc(&c.d_wx3f, xp.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_wx3f, xp.data(), xp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-    if (c.fuse7) {
-      float inv = 1.f;
-      std::vector<_Float16> xp = pack_x3_f7(c, &inv);
-      if (inv != c.x3_inv) return fail(ISL_E_STATE, "fused pair: Mconv7 scale mismatch");
-      if (!c.d_wx3f7) HIP_OK(hipMalloc(&c.d_wx3f7, xp.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_wx3f7, xp.data(), xp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-    if (c.fuse6 || c.fuse7) {   // the pair's permuted two-launch form
-      const ConvLayer pc = f7_permuted(c);
-      float inv = 1.f;
-      std::vector<_Float16> xp = pack_x3(pc, c.bco, &inv);
-      if (inv != c.x3_inv) return fail(ISL_E_STATE, "fused pair: permuted scale mismatch");
-      if (!c.d_wx3p) HIP_OK(hipMalloc(&c.d_wx3p, xp.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_wx3p, xp.data(), xp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-      if (c.fuse6) {
-        std::vector<float> b2(bp.size(), 0.f), s2(sp.size(), 0.f);
-        std::copy(pc.b.begin(), pc.b.end(), b2.begin());
-        if (c.act == ACT_PRELU) std::copy(pc.s.begin(), pc.s.end(), s2.begin());
-        if (!c.d_bp) HIP_OK(hipMalloc(&c.d_bp, b2.size() * sizeof(float)));
-        if (!c.d_sp) HIP_OK(hipMalloc(&c.d_sp, s2.size() * sizeof(float)));
-        HIP_OK(hipMemcpy(c.d_bp, b2.data(), b2.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(c.d_sp, s2.data(), s2.size() * sizeof(float), hipMemcpyHostToDevice));
-      }
-    }
-    if (c.x3_wide) {
-      float inv = 1.f;
-      std::vector<_Float16> xp = pack_x3(c, 256, &inv);
-      if (!c.d_wx3w) HIP_OK(hipMalloc(&c.d_wx3w, xp.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_wx3w, xp.data(), xp.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-#ifdef ISLPOSE_DEV
-    if (c.k == 3 && c.cout % 4 == 0) {
-      std::vector<_Float16> up = pack_wino_x3(c, &c.wx3_inv);
-      if (!c.d_wux3) HIP_OK(hipMalloc(&c.d_wux3, up.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_wux3, up.data(), up.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-#endif
-    if (c.k == 3 && c.cout % 64 == 0 && !rgb_layer(c)) {
-      std::vector<_Float16> up = pack_wino_f16(c, &c.ww_inv);
-      if (!c.d_ww) HIP_OK(hipMalloc(&c.d_ww, up.size() * sizeof(_Float16)));
-      HIP_OK(hipMemcpy(c.d_ww, up.data(), up.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    }
-    if (c.wbco) {
-      std::vector<float> up = pack_wino(c);
-      if (!c.d_wu) HIP_OK(hipMalloc(&c.d_wu, up.size() * sizeof(float)));
-      HIP_OK(hipMemcpy(c.d_wu, up.data(), up.size() * sizeof(float), hipMemcpyHostToDevice));
+    for (int p = 0; p < PB_COUNT; ++p) {
+      if (p >= PB_BIAS_PERM && !c.fuse6) continue;   // Mconv6 of a pair's permuted two-launch form
+      const std::vector<float> v = build_param(c, p, param_pad(c));
+      if (const int rc = upload(c.par[p], v.data(), v.size() * sizeof(float))) return rc;
     }
   }
+  if (const int rc = upload_packs(net, false)) return rc;
   // the flags are zeroed by blocking copies (complete on return, like the weight uploads above),
   // so every later run on any stream sees them zeroed -- no device-wide drain
   if (!net->d_flag) {
@@ -1287,10 +899,10 @@ static ConvLaunch basic_launch(const isl_net* net, const std::vector<Act>& act, 
   ConvLaunch L;
   L.in = in.base; L.in_pad = in.pad; L.in_cs = in.cs; L.in_coff = op.in_coff;
   L.out = out.base; L.out_pad = out.pad; L.out_cs = out.cs; L.out_coff = op.out_coff;
-  L.wpk = c.d_w; L.bias = c.d_b; L.slope = c.d_s;
+  L.wpk = (const float*)c.pack(PK_DIRECT); L.bias = c.param(PB_BIAS); L.slope = c.param(PB_SLOPE);
   L.n = in.n; L.H = in.H; L.W = in.W; L.ks = c.k; L.cin_chunks = c.cin_phys / 8;
   L.cout = c.cout; L.bco = c.bco; L.act = c.act;
-  L.wx3 = c.d_wx3; L.wscale_inv = c.x3_inv; L.range_flag = net->d_flag;
+  L.wx3 = c.pack(PK_X3); L.wscale_inv = c.inv[PK_X3]; L.range_flag = net->d_flag;
   L.allow_split = net->split_k;
   return L;
 }
@@ -1305,7 +917,7 @@ static int c12_form(const isl_net* net, const std::vector<Act>& act, size_t k, b
   const Op& op = net->ops[k];
   const int c12m = c12_mode();
   if (!(net->algo == ISL_ALGO_X3 && op.type == 0 && fuse_pools && c12m && k + 2 < net->ops.size() &&
-        net->layers[op.layer].d_wrgb && rgb_kernel_enabled()))
+        rgb_layer(net->layers[op.layer]) && rgb_kernel_enabled()))
     return 0;
   const Op& o2 = net->ops[k + 1];
   const Op& pl = net->ops[k + 2];
@@ -1318,10 +930,9 @@ static int c12_form(const isl_net* net, const std::vector<Act>& act, size_t k, b
   }
   if (!only) return 0;
   ConvLaunch L1 = basic_launch(net, act, op), L2 = basic_launch(net, act, o2);
-  L1.wx3 = net->layers[op.layer].d_wrgb;
+  L1.wx3 = net->layers[op.layer].pack(PK_RGB, h16);
   if (h16) {   // the one-term form: the hi-only packs of both layers
-    L1.wx3 = net->layers[op.layer].d_hrgb;
-    L2.wx3 = net->layers[o2.layer].d_hx3;
+    L2.wx3 = net->layers[o2.layer].pack(PK_X3, true);
     L1.f16 = L2.f16 = 1;
     L1.act16 = L2.act16 = a16 ? 1 : 0;   // (the pooled map / pair-max buffer is fp16)
   }
@@ -1407,14 +1018,11 @@ static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& 
       const Act& o7 = act[op7.out];
       L = basic_launch(net, act, op);
       L.out = o7.base; L.out_pad = o7.pad; L.out_cs = o7.cs; L.out_coff = op7.out_coff;
-      L.wx3 = c6.d_wx3f ? c6.d_wx3f : c6.d_wx3;
-      L.wx3f7 = c7.d_wx3f7; L.bias7 = c7.d_b; L.slope7 = c7.d_s; L.wscale7_inv = c7.x3_inv;
+      L.wx3 = c6.pack(c6.pair6_kind(), h16);
+      L.wx3f7 = c7.pack(PK_X3F7, h16); L.bias7 = c7.param(PB_BIAS); L.slope7 = c7.param(PB_SLOPE);
+      L.wscale7_inv = c7.inv[PK_X3];
       L.cout7 = c7.cout; L.act7 = c7.act;
-      if (h16) {
-        L.f16 = 1;
-        L.wx3 = c6.d_hx3f ? c6.d_hx3f : c6.d_hx3;
-        L.wx3f7 = c7.d_hx3f7;
-      }
+      if (h16) L.f16 = 1;
       if (a16) store16(L, k + 1);
       st.kind = Step::PAIR;
       st.nops = 2;
@@ -1459,11 +1067,11 @@ static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& 
     const ConvLayer& c = net->layers[op.layer];
     L = basic_launch(net, act, op);
     if (net->algo == ISL_ALGO_WINO && c.wbco) {
-      L.wpk = c.d_wu; L.bco = c.wbco;
+      L.wpk = (const float*)c.pack(PK_WINO); L.bco = c.wbco;
       st.kind = Step::WINO;
 #ifdef ISLPOSE_DEV
-    } else if (net->algo == ISL_ALGO_X3 && c.d_wux3 && x3_wino_enabled() && vin_buf < 0) {
-      L.wx3 = c.d_wux3; L.wscale_inv = c.wx3_inv;
+    } else if (net->algo == ISL_ALGO_X3 && owns_pack(c, PK_WINO_X3) && x3_wino_enabled() && vin_buf < 0) {
+      L.wx3 = c.pack(PK_WINO_X3); L.wscale_inv = c.inv[PK_WINO_X3];
       st.kind = Step::WINO_X3;
 #endif
     } else if (net->algo == ISL_ALGO_X3 && x3_fits(L)) {
@@ -1471,27 +1079,26 @@ static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& 
         const Act& hb = act[net->ops[vin_buf].hbuf];
         ConvLaunch Lv = L;
         Lv.in = hb.base; Lv.in_cs = hb.cs; Lv.in_coff = 0; Lv.vin = 1;
-        if (x3_vin_ok(Lv) && !(c.d_wrgb && x3_rgb_fits(L))) L = Lv;
+        if (x3_vin_ok(Lv) && !(rgb_layer(c) && x3_rgb_fits(L))) L = Lv;
         else st.late_pool = vin_buf;   // no variant: the pool after all
         vin_buf = -1;
       }
       const bool perm = k == perm_op || (perm_op != (size_t)-1 && k == perm_op + 1);
+      int kind = PK_X3;
       if (perm && k == perm_op) {
         // Mconv6 of the pair's two launches: output channels in the fused K order, its K
         // summed in one sequence as the fused kernel does (no ranges)
-        L.wx3 = c.d_wx3p; L.bias = c.d_bp; L.slope = c.d_sp;
+        kind = PK_X3P; L.bias = c.param(PB_BIAS_PERM); L.slope = c.param(PB_SLOPE_PERM);
         L.allow_split = 0;
       } else if (perm) {
-        L.wx3 = c.d_wx3p;   // Mconv7 reading them through that channel map
+        kind = PK_X3P;   // Mconv7 reading them through that channel map
       } else if (c.x3_wide) {   // 256-channel tiles, two pairs per step, where the grid is big enough
         ConvLaunch Lw = L;
         Lw.bco = 256;
-        if (x3_wide1(Lw)) { L.bco = 256; L.wx3 = c.d_wx3w; }
+        if (x3_wide1(Lw)) { L.bco = 256; kind = PK_X3_WIDE; }
       }
-      if (h16) {
-        L.f16 = 1;
-        L.wx3 = perm ? c.d_hx3p : L.bco == 256 && c.x3_wide ? c.d_hx3w : c.d_hx3;
-      }
+      L.wx3 = c.pack(kind, h16);
+      if (h16) L.f16 = 1;
       if (a16) store16(L, k);
       // the next op pools this conv's output: write pair maxima to its half-width buffer
       if (k + 1 < nops && net->ops[k + 1].type == 1 && net->ops[k + 1].in == op.out && op.out_coff == 0 &&
@@ -1508,15 +1115,15 @@ static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& 
                              (k + 1 < nops && net->ops[k + 1].type == 1 && net->ops[k + 1].in == op.out);
       const bool folds = far && (far->fold_ws_off[k] >= 0 || far->fold_tab_off[k] >= 0);
       ConvLaunch Lw = L;
-      Lw.wx3 = c.d_ww;
-      Lw.wscale_inv = c.ww_inv;
-      if (!h16 && !perm && !pool_side && w2_enabled(L) && c.d_ww && !L.vin && !L.hpool && !folds &&
+      Lw.wx3 = c.pack(PK_WINO_F16);
+      Lw.wscale_inv = c.inv[PK_WINO_F16];
+      if (!h16 && !perm && !pool_side && w2_enabled(L) && owns_pack(c, PK_WINO_F16) && !L.vin && !L.hpool && !folds &&
           x3_split_ranges(L, nullptr) <= 1 && wino_f16_fits(Lw)) {
         L = Lw;
         st.kind = Step::W2;
         st.code[0] = x3_variant_code(X3V_W2, 3, 128, 64);
-      } else if (c.d_wrgb && x3_rgb_fits(L) && rgb_kernel_enabled() && !L.vin) {
-        L.wx3 = h16 ? c.d_hrgb : c.d_wrgb;
+      } else if (rgb_layer(c) && x3_rgb_fits(L) && rgb_kernel_enabled() && !L.vin) {
+        L.wx3 = c.pack(PK_RGB, h16);
         st.kind = Step::X3_RGB;
         st.covered = true;
       } else {
@@ -1571,7 +1178,7 @@ static int plan_fold(isl_net* net, hipStream_t s) {
     if (j > 0 && net->ops[j - 1].type == 1 && net->ops[j - 1].out == op.in) return false;
     if (j + 1 < nops && net->ops[j + 1].type == 1 && net->ops[j + 1].in == op.out) return false;
     const ConvLayer& c = net->layers[op.layer];
-    if (c.d_wrgb) return false;
+    if (rgb_layer(c)) return false;
     return x3_fold_ok(basic_launch(net, net->act, op));
   };
   struct Prod { size_t k; int S; long long off; std::vector<size_t> cons; };
@@ -1581,7 +1188,7 @@ static int plan_fold(isl_net* net, hipStream_t s) {
     const Op& op = net->ops[k];
     if (!is_conv_x3(k)) continue;
     const ConvLayer& c = net->layers[op.layer];
-    if (c.cout % 8 || c.d_wrgb) continue;
+    if (c.cout % 8 || rgb_layer(c)) continue;
     ConvLaunch L = basic_launch(net, net->act, op);
     bool across = false;
     const int S = x3_split_ranges(L, &across);
@@ -1645,9 +1252,9 @@ static int plan_fold(isl_net* net, hipStream_t s) {
         f.ws = ar.fold_mem + p.off + cc * plane;
         f.fstride = c8 * plane;
         f.sstride = (long long)o.n * c8 * plane;
-        f.bias = c.d_b + cc * 8;
-        f.slope = c.act == ACT_PRELU ? c.d_s + cc * 8 : nullptr;
-        f.scale = c.x3_inv;
+        f.bias = c.param(PB_BIAS) + cc * 8;
+        f.slope = c.act == ACT_PRELU ? c.param(PB_SLOPE) + cc * 8 : nullptr;
+        f.scale = c.inv[PK_X3];
         f.S = p.S;
         f.act = c.act;
       }
@@ -2043,26 +1650,11 @@ int isl_net_destroy(isl_net* net) {
   if (!net) return ISL_OK;
   (void)hipSetDevice(net->device);
   for (ConvLayer& c : net->layers) {
-    if (c.d_w) (void)hipFree(c.d_w);
-    if (c.d_b) (void)hipFree(c.d_b);
-    if (c.d_s) (void)hipFree(c.d_s);
-    if (c.d_wu) (void)hipFree(c.d_wu);
-    if (c.d_wx3) (void)hipFree(c.d_wx3);
-    if (c.d_wx3w) (void)hipFree(c.d_wx3w);
-    if (c.d_wrgb) (void)hipFree(c.d_wrgb);
-    if (c.d_wux3) (void)hipFree(c.d_wux3);
-    if (c.d_ww) (void)hipFree(c.d_ww);
-    if (c.d_wx3f) (void)hipFree(c.d_wx3f);
-    if (c.d_wx3f7) (void)hipFree(c.d_wx3f7);
-    if (c.d_wx3p) (void)hipFree(c.d_wx3p);
-    if (c.d_hx3) (void)hipFree(c.d_hx3);
-    if (c.d_hx3w) (void)hipFree(c.d_hx3w);
-    if (c.d_hrgb) (void)hipFree(c.d_hrgb);
-    if (c.d_hx3f) (void)hipFree(c.d_hx3f);
-    if (c.d_hx3f7) (void)hipFree(c.d_hx3f7);
-    if (c.d_hx3p) (void)hipFree(c.d_hx3p);
-    if (c.d_bp) (void)hipFree(c.d_bp);
-    if (c.d_sp) (void)hipFree(c.d_sp);
+    for (auto& forms : c.dev)
+      for (DevBuf& d : forms)
+        if (d.p) (void)hipFree(d.p);
+    for (DevBuf& d : c.par)
+      if (d.p) (void)hipFree(d.p);
   }
   for (auto& kv : net->flag_events) {
     (void)hipEventSynchronize(kv.second);
@@ -2600,6 +2192,8 @@ int isl_debug_conv(const isl_debug_conv_desc* dp, const float* x, const float* w
 
   ConvLayer c = mk("debug", d.cin, d.cout, d.ks, d.act);
   c.w.assign(wgt, wgt + (size_t)d.cout * d.cin * d.ks * d.ks);
+  c.b.assign(bias, bias + d.cout);
+  if (d.act == ACT_PRELU) c.s.assign(slope, slope + d.cout);
   for (int i = 0; i < d.nseg; ++i) c.cmap.push_back({d.seg[i].logical, d.seg[i].phys, d.seg[i].len});
   c.cin_phys = cin_phys;
   c.bco = conv_bco_for(d.cout);
@@ -2641,9 +2235,7 @@ int isl_debug_conv(const isl_debug_conv_desc* dp, const float* x, const float* w
   if (d.hpool) pool.fill(0, pool.elems(), DBG_CANARY32, DBG_CANARY16);
 
   const size_t nb = ((size_t)d.cout + 255) / 256 * 256 + 256;   // bias / slopes padded to any channel tile
-  std::vector<float> hb(nb, 0.f), hs(nb, 0.f);
-  std::copy(bias, bias + d.cout, hb.begin());
-  if (d.act == ACT_PRELU) std::copy(slope, slope + d.cout, hs.begin());
+  const std::vector<float> hb = build_param(c, PB_BIAS, nb), hs = build_param(c, PB_SLOPE, nb);
 
   ConvLaunch L;
   L.in_pad = d.in_pad; L.in_cs = d.in_cs; L.in_coff = d.in_coff;
@@ -2653,9 +2245,7 @@ int isl_debug_conv(const isl_debug_conv_desc* dp, const float* x, const float* w
   L.allow_split = d.allow_split;
   L.vin = d.vin;
   // the choices plan_steps makes for a launch, in its order; the shape checks need no device memory
-  std::vector<_Float16> pk16;
-  std::vector<float> pk32;
-  float inv = 1.f;
+  int kind = PK_DIRECT;
   if (x3) {
     if (!x3_fits(L)) return bad("shape does not fit conv_x3");
     if (d.vin && !x3_vin_ok(L)) return bad("no pooled-input variant for this launch (x3_vin_ok)");
@@ -2671,24 +2261,19 @@ int isl_debug_conv(const isl_debug_conv_desc* dp, const float* x, const float* w
       if (!x3_hpool_ok(L)) return bad("no pair-max epilogue for this launch (x3_hpool_ok)");
       L.hpool = 1;
     }
-    pk16 = pack_x3(c, L.bco, &inv);
-    if (d.f16) pk16 = pack_hi_only(pk16, (size_t)2 * L.bco * 8);
+    kind = L.bco == 256 ? PK_X3_WIDE : PK_X3;
   } else if (rgb) {
     L.f16 = d.f16; L.act16 = d.act16;
     if (!rgb_layer(c) || !x3_rgb_fits(L)) return bad("shape does not fit the rgb kernel");
-    (void)pack_x3(c, c.bco, &inv);   // the same 2^s
-    pk16 = pack_x3_rgb(c);
-    if (d.f16) pk16 = pack_hi_only(pk16, (size_t)2 * 64 * 8);
+    kind = PK_RGB;
   } else if (d.kernel == ISL_DBG_WINO2) {
     if (d.ks != 3 || d.cout % 64 || !wino_f16_fits(L)) return bad("shape not eligible for the Winograd kernel");
-    pk16 = pack_wino_f16(c, &inv);
+    kind = PK_WINO_F16;
   } else if (d.kernel == ISL_DBG_WINO) {
     L.bco = c.wbco;
-    pk32 = pack_wino(c);
-  } else {
-    pk32 = pack_weights(c);
+    kind = PK_WINO;
   }
-  L.wscale_inv = inv;
+  const HostPack pk = build_pack(c, kind, d.f16, &L.wscale_inv);
 
   std::vector<void*> owned;
   int flag = 0;
@@ -2701,22 +2286,21 @@ int isl_debug_conv(const isl_debug_conv_desc* dp, const float* x, const float* w
     float *d_b = nullptr, *d_s = nullptr, *d_ws = nullptr;
     void* d_w = nullptr;
     int* d_flag = nullptr;
-    const size_t wbytes = pk16.empty() ? pk32.size() * 4 : pk16.size() * sizeof(_Float16);
     HIP_OK(dmalloc(&in.d, in.bytes()));
     HIP_OK(dmalloc(&out.d, out.bytes()));
     HIP_OK(dmalloc((void**)&d_b, nb * 4));
     HIP_OK(dmalloc((void**)&d_s, nb * 4));
-    HIP_OK(dmalloc(&d_w, wbytes));
+    HIP_OK(dmalloc(&d_w, pk.bytes()));
     HIP_OK(dmalloc((void**)&d_flag, 4));
     HIP_OK(hipMemcpy(in.d, in.h.data(), in.bytes(), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(out.d, out.h.data(), out.bytes(), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_b, hb.data(), nb * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_s, hs.data(), nb * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_w, pk16.empty() ? (const void*)pk32.data() : (const void*)pk16.data(), wbytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_w, pk.data(), pk.bytes(), hipMemcpyHostToDevice));
     HIP_OK(hipMemset(d_flag, 0, 4));
     L.in = (const float*)in.dev(); L.out = (float*)out.dev();
     L.bias = d_b; L.slope = d_s; L.range_flag = d_flag;
-    if (pk16.empty()) L.wpk = (const float*)d_w; else L.wx3 = d_w;
+    if (pk.f16.empty()) L.wpk = (const float*)d_w; else L.wx3 = d_w;
     if (x3) {
       const size_t need = x3_splitk_ws_floats(L);
       if (need > (64u << 20)) return bad("split-K workspace over 256 MiB");

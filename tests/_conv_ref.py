@@ -15,7 +15,7 @@ split-K partial sums added by x3_splitk_reduce) passes every term through at mos
 additions, so its error is at most gamma(n - 1) sum |terms|.  The matrix cores' internal order
 is not documented; the bound does not need it.
 
-Three-term conv_x3 (csrc/conv_x3.hip lines 1-22, pack_x3 in csrc/runtime.cpp).
+Three-term conv_x3 (csrc/conv_x3.hip lines 1-22, pack_x3 in csrc/pack.cpp).
   x = xh + xl + rx with xh = fp16(x), xl = fp16(x - xh) (the subtraction is exact in fp32).
   fp16 carries 11 bits: |x - xh| <= 2^-11 |x| while xh is a normal number, and
   |rx| <= 2^-11 |x - xh| <= 2^-22 |x| while xl is one.  An fp16 subnormal is a multiple of 2^-24,
