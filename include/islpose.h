@@ -403,6 +403,72 @@ int isl_hand_post_crops_ex(isl_net* net, int n, const int32_t* crop_w, int nscal
  * sums (the block-cooperative device routine): d_out[0] = sum(d_a[0..n)). */
 int isl_debug_np_sum(const double* d_a, int64_t n, double* d_out, void* stream);
 
+/* Diagnostic: the host-side choices of the post-processing, as data -- which kernel forms and
+ * which blur branch isl_body_post_opts / isl_hand_post* take for a geometry and the A/B
+ * environment switches as they stand at the call.  The posts call the same two host functions
+ * and launch from their result, so a test that asserts a plan asserts the branch a post at that
+ * geometry reaches.  Neither entry touches the device or needs a net.
+ *
+ * One launch of the separable resize (resize_sep_kernel): */
+typedef struct {
+  int32_t launched;   /* 0: the post launches no such resize (the fields below are zero)        */
+  int32_t ty;         /* output rows per tile (64 unless the source window caps it)             */
+  int32_t cols;       /* output columns per block: 128 or 256                                   */
+  int32_t v4;         /* the four-column vertical pass (needs width % 4 == 0, ty % 4 == 0)      */
+  int32_t bm;         /* also writes the band maxima of its output (needs ty % 16 == 0)         */
+  int32_t identity;   /* the source is copied, not interpolated                                 */
+} isl_resize_plan;
+
+enum isl_blur_branch {
+  ISL_BLUR_MULTI_F64 = 0,    /* several scales: fp64 average planes, one block per tile          */
+  ISL_BLUR_FUSED_LIVE = 1,   /* resize inside the blur, over the live-tile list                  */
+  ISL_BLUR_BAND_LIVE = 2,    /* materialised fp32 planes, live-tile list from the band maxima    */
+  ISL_BLUR_DENSE = 3         /* materialised fp32 planes, one block per tile of the dense grid   */
+};
+
+#define ISL_PLAN_SCALES 8    /* the posts take at most this many scales */
+
+typedef struct {
+  int32_t multi;        /* nscales > 1                                                          */
+  int32_t two_stage;    /* single scale whose valid size is not the frame's (x8, then to frame) */
+  int32_t fused;        /* no full-resolution heat planes: the blur resizes on the fly          */
+  int32_t fuse2;        /* two_stage and fused (the stage-2 window fits the blur's LDS window)  */
+  int32_t wide;         /* fuse2 through the wide window (development build only)               */
+  int32_t skip2;        /* stage-2 tiles no live blur window reads are skipped                  */
+  int32_t blur;         /* enum isl_blur_branch                                                 */
+  int32_t blur_bandmax; /* ISL_BLUR_DENSE only: the tiles still take the band-maxima early out  */
+  int32_t acc_ty;       /* multi: resize_acc_kernel's output rows per tile (16 or less); else 0 */
+  int32_t stage2_ty;    /* output rows per stage-2 resize tile as stage2_need_kernel counts them */
+  int32_t limb_z;       /* blocks per limb of the pair scoring (1: the one-kernel form)         */
+  /* the environment switches as read: 1 = on */
+  int32_t env_fused_blur, env_fused_wide, env_blur_list, env_blur_bands, env_resize_skip, env_resize_v4;
+  int32_t env_blur_exact;   /* ISLPOSE_BLUR_EXACT: 0, 1 or 2                                    */
+  int32_t scale_two_stage[ISL_PLAN_SCALES];   /* per scale: valid size != frame size            */
+  isl_resize_plan stage1[ISL_PLAN_SCALES];    /* x8 to the valid size (two-stage scales only)   */
+  isl_resize_plan final_rs[ISL_PLAN_SCALES];  /* the resize that lands on the frame; launched   */
+                                              /* only for a single scale that is not fused      */
+  int32_t reserved[6];
+} isl_body_post_plan;
+
+typedef struct {
+  int32_t two_stage[ISL_PLAN_SCALES];   /* per scale: valid size != crop size                   */
+  int32_t identity[ISL_PLAN_SCALES];    /* per scale: the accumulate kernel copies the source   */
+  isl_resize_plan stage1[ISL_PLAN_SCALES];   /* x8 to the valid size (two-stage scales only)    */
+  int32_t acc_ty;       /* resize_acc_kernel's output rows per tile: 16, less when a scale's    */
+                        /* source rows per output row would overflow the 40-row LDS window      */
+  int32_t cc_lds;       /* 1: components in one workgroup's LDS (h * w <= 36864); 0: the        */
+                        /* large-plane chain                                                    */
+  int32_t cc_rows, cc_chunks;   /* the large-plane chain's rows per chunk and chunks per plane  */
+  int32_t reserved[4];
+} isl_hand_post_plan;
+
+/* model_kind ISL_BODY25 / ISL_COCO, n frames of H x W, geom[nscales].  ISL_E_ARG: a NULL, a
+ * non-positive size, nscales outside 1..ISL_PLAN_SCALES, a net size below 8 or a valid size
+ * below 1. */
+int isl_debug_body_post_plan(int model_kind, int n, int H, int W, int nscales, const isl_scale_geom* geom,
+                             isl_body_post_plan* out);
+int isl_debug_hand_post_plan(int h, int w, int nscales, const isl_scale_geom* geom, isl_hand_post_plan* out);
+
 /* Diagnostic: one 3x3 convolution layer (stride 1, pad 1, bias, PReLU) of the split-fp16 path on
  * host arrays, outside any net -- shapes no graph has, such as a K loop of one or two steps.
  * x [n][cin][h][w], wgt [cout][cin][3][3], bias and slope [cout], y [n][cout][h][w], all fp32 on

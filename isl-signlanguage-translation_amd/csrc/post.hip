@@ -3149,32 +3149,52 @@ static int post_fail(int code, const char* msg) {
     }                                                       \
   } while (0)
 
+// rows per tile: `ty` lowered until the source window of a resize of vertical scale scy fits
+// the LDS rows
+static int fit_rows(int ty, double scy, bool identity) {
+  if (!identity)
+    while (ty > 1 && (ty - 1) * scy + 5.0 > (double)RS_MAXR) --ty;
+  return ty;
+}
+static int resize_rows(double scy, bool identity) {   // output rows per resize tile
+  return fit_rows(RS_TY, scy, identity);
+}
+static bool env_on(const char* name) {   // an A/B switch that is on unless set to 0 (read per call)
+  const char* e = getenv(name);
+  return !(e && e[0] == '0');
+}
+// The form launch_resize runs for a source of vertical scale scy onto ow columns; want_bm: the
+// caller has a band-maxima buffer for it (mode 1).  (ISLPOSE_RESIZE_V4=0: the one-column vertical
+// pass everywhere; A/B, per call)
+static isl_resize_plan resize_form(double scy, bool identity, int ow, int mode, bool want_bm) {
+  isl_resize_plan f{};
+  f.launched = 1;
+  f.identity = identity;
+  f.ty = resize_rows(scy, identity);
+  const bool v4 = mode == 1 && !identity && ow % 4 == 0 && f.ty % 4 == 0 && env_on("ISLPOSE_RESIZE_V4");
+  f.bm = want_bm && mode == 1 && f.ty % BM_ROWS == 0;
+  f.v4 = f.bm ? v4 && f.ty == 4 * BM_ROWS : v4;
+  // 128-column blocks unless 256 pads less (it never does); the BM and V4 forms are 128 wide
+  f.cols = f.bm || f.v4 || (ow + 127) / 128 * 128 <= (ow + RS_TX - 1) / RS_TX * RS_TX ? 128 : RS_TX;
+  return f;
+}
 // planar resize of n*nch planes (see resize_sep_kernel); rows per tile sized to the LDS window
 // bandmax (mode 1): also write the band maxima of the output planes (resize_sep_kernel BM) when
 // the tiles align with the bands; *bm_done says whether they were written
-static int resize_rows(const MapSrc& m) {   // output rows per resize tile
-  int ty = RS_TY;
-  if (!m.identity)
-    while (ty > 1 && (ty - 1) * m.scy + 5.0 > (double)RS_MAXR) --ty;
-  return ty;
-}
-// the band-maxima form of launch_resize runs (and so `need` may be given)
-static bool resize_bm_v4(const MapSrc& m, int ow) {
-  const char* v4e = getenv("ISLPOSE_RESIZE_V4");
-  return !m.identity && ow % 4 == 0 && resize_rows(m) == 4 * BM_ROWS && !(v4e && v4e[0] == '0');
-}
+// `f`: resize_form of this launch (the posts take it from their plan)
 static int launch_resize(const MapSrc& m, int n, int nch, int oh, int ow, int mode, float div_f, void* out,
-                         hipStream_t s, float* bandmax = nullptr, bool* bm_done = nullptr,
+                         hipStream_t s, const isl_resize_plan& f, float* bandmax = nullptr, bool* bm_done = nullptr,
                          const unsigned char* need = nullptr) {
-  const int ty = resize_rows(m);
+  // (the kernels trap on a tile taller than the LDS window: never launch a ty the source did not size)
+  if (!f.launched || (f.bm && !bandmax) || (bool)f.identity != (bool)m.identity ||
+      f.ty != resize_rows(m.scy, m.identity))
+    return post_fail(ISL_E_STATE, "resize: the plan does not fit the launch");
+  const int ty = f.ty;
   const long long ty_tiles = (oh + ty - 1) / ty;
   if (ty_tiles > 65535) return post_fail(ISL_E_ARG, "resize: output too tall");
   if (bm_done) *bm_done = false;
-  // (ISLPOSE_RESIZE_V4=0: the one-column vertical pass everywhere; A/B, per call)
-  const char* v4e = getenv("ISLPOSE_RESIZE_V4");
-  const bool v4 = mode == 1 && !m.identity && ow % 4 == 0 && ty % 4 == 0 && !(v4e && v4e[0] == '0');
-  if (bandmax && mode == 1 && ty % BM_ROWS == 0) {
-    if (v4 && ty == 4 * BM_ROWS)
+  if (f.bm) {
+    if (f.v4)
       hipLaunchKernelGGL((resize_sep_kernel<128, 4, 8, true, true>), dim3(n * nch, (unsigned)ty_tiles, (ow + 127) / 128),
                          dim3(128), 0, s, m, nch, oh, ow, ty, mode, div_f, out, bandmax, need);
     else if (need)
@@ -3186,7 +3206,7 @@ static int launch_resize(const MapSrc& m, int n, int nch, int oh, int ow, int mo
     if (bm_done) *bm_done = true;
     return ISL_OK;
   }
-  if (v4) {
+  if (f.v4) {
     hipLaunchKernelGGL((resize_sep_kernel<128, 4, 8, false, true>), dim3(n * nch, (unsigned)ty_tiles, (ow + 127) / 128),
                        dim3(128), 0, s, m, nch, oh, ow, ty, mode, div_f, out);
     PHIP(hipGetLastError());
@@ -3198,7 +3218,7 @@ static int launch_resize(const MapSrc& m, int n, int nch, int oh, int ow, int mo
   // vertical pass unrolled by 4: Mode R batch-32 post -2.5 %, batch 1 -1.8 %; staging the
   // source window in LDS lost 20 %, 16 source rows in flight instead of 8 gained nothing
   // (tools/resize_ab.py, profiles/r04/r4d/resize_ab.json)
-  if ((ow + 127) / 128 * 128 <= (ow + RS_TX - 1) / RS_TX * RS_TX)
+  if (f.cols == 128)
     hipLaunchKernelGGL((resize_sep_kernel<128, 4>), dim3(n * nch, (unsigned)ty_tiles, (ow + 127) / 128), dim3(128), 0, s,
                        m, nch, oh, ow, ty, mode, div_f, out);
   else
@@ -3299,6 +3319,98 @@ static int post_opts_resolve(const isl_post_opts* opts, isl_post_opts* out, cons
   return ISL_OK;
 }
 
+static_assert(ISL_PLAN_SCALES == MAX_SCALES, "the plan structs hold one slot per scale");
+
+static bool plan_geom_ok(int nscales, const isl_scale_geom* geom) {
+  if (nscales <= 0 || nscales > MAX_SCALES || !geom) return false;
+  for (int si = 0; si < nscales; ++si)
+    if (geom[si].net_h < 8 || geom[si].net_w < 8 || geom[si].valid_h < 1 || geom[si].valid_w < 1) return false;
+  return true;
+}
+
+// What isl_body_post_opts chooses on the host for n frames of H x W (no device work): the
+// post launches from this plan, and isl_debug_body_post_plan returns it.
+static void body_post_plan(int kind, int n, int H, int W, int nscales, const isl_scale_geom* geom,
+                           isl_body_post_plan* p) {
+  memset(p, 0, sizeof(*p));
+  const int nlimbs = kind == ISL_BODY25 ? 24 : 19;
+  const isl_scale_geom& g0 = geom[0];
+  const bool multi = nscales > 1;
+  // single scale with the net input at frame size (one x8 resize): fuse resize + blur,
+  // no full-resolution heat planes
+  // single scale, two stages (Mode R on large frames: 184 x 327 -> 1080 x 1920): the
+  // second resize is a strong upsampling whose full-resolution planes cost more HBM
+  // traffic than the on-the-fly resize; fused too when a blur tile's source window fits
+  // the LDS window (~1/5.2 and below; at 368 x 656, scale 1/2, it does not)
+  // (the wide window takes stage-2 scales down to ~1/2: Mode R at 368 x 656)
+  auto window_fits = [&](int rows, int cols) {
+    return 41.0 * g0.valid_h / H + 6.0 <= rows && 217.0 * g0.valid_w / W + 6.0 <= cols;
+  };
+  const bool two = !multi && !(g0.valid_h == H && g0.valid_w == W);
+  const bool fuse2_small = two && window_fits(NMS_SRC_ROWS, NMS_SRC_COLS);
+  p->env_fused_wide = fused_wide_enabled();
+  p->env_fused_blur = fused_blur_enabled();
+  const bool fuse2 = two && (fuse2_small || (window_fits(NMS_WSRC_ROWS, NMS_WSRC_COLS) && p->env_fused_wide));
+  const bool fused = !multi && (!two || fuse2) && p->env_fused_blur;
+  p->multi = multi;
+  p->two_stage = two;
+  p->fuse2 = fuse2;
+  p->wide = fuse2 && !fuse2_small;
+  p->fused = fused;
+  // ISLPOSE_BLUR_LIST=0: the band-maxima early out inside every tile's block instead of a live
+  // list (A/B; per call)
+  p->env_blur_list = env_on("ISLPOSE_BLUR_LIST");
+  // single scale, materialised planes: the band maxima of the final resize (blur early out)
+  // (ISLPOSE_BLUR_BANDS=0: without, A/B; read per call)
+  p->env_blur_bands = env_on("ISLPOSE_BLUR_BANDS");
+  const bool bands = !fused && !multi && p->env_blur_bands;
+  // two-stage frames: stage-2 tiles that no live window reads are skipped (stage2_need_kernel;
+  // ISLPOSE_RESIZE_SKIP=0 off, A/B, per call), which takes the band-maxima V4 form of both stages
+  p->env_resize_skip = env_on("ISLPOSE_RESIZE_SKIP");
+  p->env_resize_v4 = env_on("ISLPOSE_RESIZE_V4");
+  p->env_blur_exact = blur_exact_only();
+  const double scy2 = 1.0 / ((double)H / g0.valid_h);
+  const isl_resize_plan s1bm = resize_form(1.0 / 8.0, false, g0.valid_w, 1, true);
+  const isl_resize_plan s2bm = resize_form(scy2, false, W, 1, true);
+  p->skip2 = !fused && !multi && two && bands && p->env_blur_list && p->env_resize_skip && s1bm.bm && s1bm.v4 &&
+             s2bm.bm && s2bm.v4;
+  p->stage2_ty = resize_rows(scy2, false);
+  int acc_ty = RA_TY;
+  for (int si = 0; si < nscales; ++si) {
+    const isl_scale_geom& g = geom[si];
+    const bool two_stage = !(g.valid_h == H && g.valid_w == W);
+    p->scale_two_stage[si] = two_stage;
+    // stage 1: cv2.resize(fx=fy=8); stage 2: cv2.resize(crop, (W, H)), scale = 1 / (H / valid_h)
+    if (two_stage) p->stage1[si] = resize_form(1.0 / 8.0, false, g.valid_w, 1, p->skip2);
+    const double scy = two_stage ? 1.0 / ((double)H / g.valid_h) : 1.0 / 8.0;
+    if (multi) acc_ty = fit_rows(acc_ty, scy, false);   // every scale's final resize, one fp64 pass
+    else if (!fused) p->final_rs[si] = resize_form(scy, false, W, 1, bands);
+  }
+  p->acc_ty = multi ? acc_ty : 0;
+  if (multi) p->blur = ISL_BLUR_MULTI_F64;
+  else if (fused) p->blur = ISL_BLUR_FUSED_LIVE;
+  else if (p->final_rs[0].bm && p->env_blur_list) p->blur = ISL_BLUR_BAND_LIVE;
+  else p->blur = ISL_BLUR_DENSE;
+  p->blur_bandmax = p->blur == ISL_BLUR_DENSE && p->final_rs[0].bm;
+  // a frame per call: the scoring over Z blocks per limb (MODE 1), then ranks and matches (MODE 2);
+  // ISLPOSE_LIMB_SPLIT=0: one block per limb (A/B; read per call)
+  // ISLPOSE_LIMB_Z=z: z blocks per limb (A/B; read per call).  A 1080p frame's scoring: 10 / 32 /
+  // 64 blocks per limb 70.7 / 34.5 / 40.5 us (profiles/r06/lk/lz/); each pair is scored whole
+  // by one block, so the slicing changes no sum
+  const char* lzs = getenv("ISLPOSE_LIMB_Z");
+  p->limb_z = !env_on("ISLPOSE_LIMB_SPLIT") || n * nlimbs >= 128 ? 1
+              : lzs ? std::max(1, std::min(64, atoi(lzs))) : std::max(1, std::min(32, 1024 / (n * nlimbs)));
+}
+
+extern "C" int isl_debug_body_post_plan(int model_kind, int n, int H, int W, int nscales, const isl_scale_geom* geom,
+                                        isl_body_post_plan* out) {
+  if ((model_kind != ISL_BODY25 && model_kind != ISL_COCO) || n <= 0 || H <= 0 || W <= 0 || !out ||
+      !plan_geom_ok(nscales, geom))
+    return post_fail(ISL_E_ARG, "isl_debug_body_post_plan: bad argument");
+  body_post_plan(model_kind, n, H, W, nscales, geom, out);
+  return ISL_OK;
+}
+
 extern "C" int isl_body_post(isl_net* net, int n, int H, int W, int nscales, const isl_scale_geom* geom,
                              const float* const* d_paf, const float* const* d_heat, const isl_caps* caps,
                              void* d_result, void* stream) {
@@ -3323,22 +3435,9 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
   int rc = isl_body_layout(kind, caps, &lay);
   if (rc) return rc;
   // ---- scratch plan ----
-  const bool multi = nscales > 1;
-  // single scale with the net input at frame size (one x8 resize): fuse resize + blur,
-  // no full-resolution heat planes
-  // single scale, two stages (Mode R on large frames: 184 x 327 -> 1080 x 1920): the
-  // second resize is a strong upsampling whose full-resolution planes cost more HBM
-  // traffic than the on-the-fly resize; fused too when a blur tile's source window fits
-  // the LDS window (~1/5.2 and below; at 368 x 656, scale 1/2, it does not)
-  // (the wide window takes stage-2 scales down to ~1/2: Mode R at 368 x 656)
-  auto window_fits = [&](int rows, int cols) {
-    return 41.0 * geom[0].valid_h / H + 6.0 <= rows && 217.0 * geom[0].valid_w / W + 6.0 <= cols;
-  };
-  const bool two = !multi && !(geom[0].valid_h == H && geom[0].valid_w == W);
-  const bool fuse2_small = two && window_fits(NMS_SRC_ROWS, NMS_SRC_COLS);
-  const bool fuse2 = two && (fuse2_small || (window_fits(NMS_WSRC_ROWS, NMS_WSRC_COLS) && fused_wide_enabled()));
-  const bool wide = fuse2 && !fuse2_small;
-  const bool fused = !multi && ((geom[0].valid_h == H && geom[0].valid_w == W) || fuse2) && fused_blur_enabled();
+  isl_body_post_plan plan;  // every choice between kernel forms and blur branches (body_post_plan)
+  body_post_plan(kind, n, H, W, nscales, geom, &plan);
+  const bool multi = plan.multi, wide = plan.wide, fused = plan.fused, skip2 = plan.skip2;
   const size_t heat_bytes = fused ? 0 : (size_t)n * nparts * H * W * (multi ? 8 : 4);
   size_t mid_bytes = 0;
   for (int si = 0; si < nscales; ++si) {
@@ -3350,30 +3449,15 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
   const size_t pair_bytes = (size_t)n * nlimbs * caps->max_pairs * (8 + 4 + 4);
   const size_t used_bytes = (size_t)n * nlimbs * 2 * caps->max_peaks;
   const size_t n_tiles_all = (size_t)((W + NMS_TX - 1) / NMS_TX) * ((H + NMS_TY - 1) / NMS_TY) * n * nparts;
-  // ISLPOSE_BLUR_LIST=0: the band-maxima early out inside every tile's block instead of a live
-  // list (A/B; per call)
-  const char* ble = getenv("ISLPOSE_BLUR_LIST");
-  const bool band_list = !(ble && ble[0] == '0');
+  const bool band_list = plan.env_blur_list;
   // single scale, materialised planes: the band maxima of the final resize (blur early out)
-  // (ISLPOSE_BLUR_BANDS=0: without, A/B; read per call)
-  const char* bme = getenv("ISLPOSE_BLUR_BANDS");
-  const bool bands_on = !(bme && bme[0] == '0');
-  const size_t bm_bytes = (!fused && !multi && bands_on) ? (size_t)n * nparts * ((H + BM_ROWS - 1) / BM_ROWS) * words * 4 : 0;
+  const size_t bm_bytes = (!fused && !multi && plan.env_blur_bands) ? (size_t)n * nparts * ((H + BM_ROWS - 1) / BM_ROWS) * words * 4 : 0;
   const size_t live_bytes = (fused || (bm_bytes && band_list)) ? (n_tiles_all + 1) * sizeof(int) : 0;
   const size_t amb_bytes = (n_tiles_all + 1) * sizeof(int);   // the filter's undecided tiles
-  // two-stage frames: stage-2 tiles that no live window reads are skipped (stage2_need_kernel;
-  // ISLPOSE_RESIZE_SKIP=0 off, A/B, per call).  bm1: the stage-1 planes' band maxima
-  const char* rse = getenv("ISLPOSE_RESIZE_SKIP");
+  // two-stage frames: stage-2 tiles that no live window reads are skipped (stage2_need_kernel).
+  // bm1: the stage-1 planes' band maxima
   const isl_scale_geom& g0 = geom[0];
-  MapSrc m2probe{};
-  m2probe.identity = 0;
-  m2probe.scy = 1.0 / ((double)H / g0.valid_h);
-  MapSrc m1probe{};
-  m1probe.identity = 0;
-  m1probe.scy = 1.0 / 8.0;
-  const bool skip2 = !fused && !multi && two && bm_bytes && band_list && !(rse && rse[0] == '0') &&
-                     resize_bm_v4(m1probe, g0.valid_w) && resize_bm_v4(m2probe, W);
-  const int ty2 = resize_rows(m2probe), ry_tiles = (H + ty2 - 1) / ty2, rx_tiles = (W + 127) / 128;
+  const int ty2 = plan.stage2_ty, ry_tiles = (H + ty2 - 1) / ty2, rx_tiles = (W + 127) / 128;
   const size_t bm1_bytes = skip2 ? (size_t)n * nparts * ((g0.valid_h + BM_ROWS - 1) / BM_ROWS) * ((g0.valid_w + 63) / 64) * 4 : 0;
   const size_t lmid_bytes = skip2 ? n_tiles_all : 0;
   const size_t need_bytes = skip2 ? (size_t)n * nparts * ry_tiles * rx_tiles : 0;
@@ -3430,7 +3514,8 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
       float* mh = (float*)midp;
       midp += (size_t)n * g.valid_h * g.valid_w * nparts * 4;
       bool bm1_done = false;
-      if ((rc = launch_resize(lh, n, nparts, g.valid_h, g.valid_w, 1, 1.f, mh, s, skip2 ? bm1 : nullptr, &bm1_done)))
+      if ((rc = launch_resize(lh, n, nparts, g.valid_h, g.valid_w, 1, 1.f, mh, s, plan.stage1[si],
+                              skip2 ? bm1 : nullptr, &bm1_done)))
         return rc;
       if (skip2 && !bm1_done) return post_fail(ISL_E_HIP, "body post: stage-1 band maxima not written");
       // the PAF's stage 1 is not materialised: limb_kernel samples both stages on demand
@@ -3460,17 +3545,18 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
                            tyl, nt, thre1, ty2, ry_tiles, rx_tiles, live_mid, need);
         PHIP(hipGetLastError());
       }
-      if ((rc = launch_resize(fh, n, nparts, H, W, 1, div_f, heat, s, bandmax, &bm_done, need))) return rc;
+      if ((rc = launch_resize(fh, n, nparts, H, W, 1, div_f, heat, s, plan.final_rs[si], bandmax, &bm_done, need)))
+        return rc;
     }
     ga.paf[si] = fp;
   }
   if (multi) {
     // heatmap_avg += heatmap_avg + heatmap / len(m) over the scales (body.py:80, the
     // doubling quirk) in fp64 registers, one store (resize_acc_kernel)
-    int ty = RA_TY;
+    const int ty = plan.acc_ty;   // (the kernel traps on a taller tile than a scale's window allows)
     for (int si = 0; si < nscales; ++si)
-      if (!fin.m[si].identity)
-        while (ty > 1 && (ty - 1) * fin.m[si].scy + 5.0 > (double)RS_MAXR) --ty;
+      if (ty < 1 || fit_rows(ty, fin.m[si].scy, fin.m[si].identity) != ty)
+        return post_fail(ISL_E_STATE, "body post: the plan's rows per tile do not fit a scale");
     const long long ty_tiles = (H + ty - 1) / ty;
     if (ty_tiles > 65535) return post_fail(ISL_E_ARG, "body post: frame too tall");
     hipLaunchKernelGGL(resize_acc_kernel, dim3(n * nparts, (unsigned)ty_tiles, (W + RS_TX - 1) / RS_TX), dim3(RS_TX),
@@ -3481,11 +3567,13 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
   dim3 gb((W + NMS_TX - 1) / NMS_TX, (H + NMS_TY - 1) / NMS_TY, n * nparts);
   tile_prof_arm((size_t)gb.x * gb.y * gb.z, s);
   const int tx = (int)gb.x, tyl = (int)gb.y;
-  if (multi) {
+  if (!multi && !fused && bm_done != (bool)plan.final_rs[0].bm)
+    return post_fail(ISL_E_STATE, "body post: the final resize did not follow the plan");
+  if (plan.blur == ISL_BLUR_MULTI_F64) {
     if ((rc = launch_blur<double, false>(gb, s, (const double*)heat, H, W, words, mask, thre1, 0, MapSrc{}, 0, nullptr,
                                          nullptr, tx, tyl, nullptr, amb, true)))
       return rc;
-  } else if (fused) {
+  } else if (plan.blur == ISL_BLUR_FUSED_LIVE) {
     // live-tile list (low-res bound), then the fused blur over live tiles only
     const int n_tiles = (int)(gb.x * gb.y * gb.z);
     // (mask, live_count: zeroed by init_records_kernel)
@@ -3508,7 +3596,7 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
                                          thre1, 0, fused_src, nparts, live, live_count, tx, tyl, nullptr, amb, true)))
         return rc;
     }
-  } else if (bm_done && band_list) {
+  } else if (plan.blur == ISL_BLUR_BAND_LIVE) {
     // live-tile list (the band maxima), then the blur over live tiles only
     const int n_tiles = (int)(gb.x * gb.y * gb.z);
     // (mask, live_count: zeroed by init_records_kernel)
@@ -3519,7 +3607,8 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
                                         thre1, 0, MapSrc{}, 0, live, live_count, tx, tyl, nullptr, amb, true)))
       return rc;
   } else if ((rc = launch_blur<float, false>(gb, s, (const float*)heat, H, W, words, mask, thre1, 0, MapSrc{}, 0, nullptr,
-                                             nullptr, tx, tyl, bm_done ? (const float*)bandmax : nullptr, amb, true))) {
+                                             nullptr, tx, tyl, plan.blur_bandmax ? (const float*)bandmax : nullptr, amb,
+                                             true))) {
     return rc;
   }
   PHIP(hipGetLastError());
@@ -3552,15 +3641,9 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
   }
   ga.thre2 = po.thre2;
   ga.max_people = po.max_people;
-  // a frame per call: the scoring over Z blocks per limb (MODE 1), then ranks and matches (MODE 2);
-  // ISLPOSE_LIMB_SPLIT=0: one block per limb (A/B; read per call)
-  const char* lse = getenv("ISLPOSE_LIMB_SPLIT");
-  // ISLPOSE_LIMB_Z=z: z blocks per limb (A/B; read per call).  A 1080p frame's scoring: 10 / 32 /
-  // 64 blocks per limb 70.7 / 34.5 / 40.5 us (profiles/r06/lk/lz/); each pair is scored whole
-  // by one block, so the slicing changes no sum
-  const char* lzs = getenv("ISLPOSE_LIMB_Z");
-  const int lz = (lse && lse[0] == '0') || n * nlimbs >= 128 ? 1
-                 : lzs ? std::max(1, std::min(64, atoi(lzs))) : std::max(1, std::min(32, 1024 / (n * nlimbs)));
+  // the scoring over Z blocks per limb (MODE 1), then ranks and matches (MODE 2), or one block
+  // per limb (body_post_plan)
+  const int lz = plan.limb_z;
   if (lz > 1) {
     hipLaunchKernelGGL(limb_kernel<1>, dim3(nlimbs, n, lz), dim3(256), 0, s, ga);
     hipLaunchKernelGGL(limb_kernel<2>, dim3(nlimbs, n), dim3(256), 0, s, ga);
@@ -3616,6 +3699,34 @@ static size_t hand_post_bytes(int n, int h, int w, int nscales, const isl_scale_
          up(bs_bytes) + up(amb_bytes);
 }
 
+// What hand_post_launch chooses on the host for crops of h x w (no device work): the launch
+// follows this plan, and isl_debug_hand_post_plan returns it.
+static void hand_post_plan(int h, int w, int nscales, const isl_scale_geom* geom, isl_hand_post_plan* p) {
+  memset(p, 0, sizeof(*p));
+  int ty = RA_TY;
+  for (int si = 0; si < nscales; ++si) {
+    const isl_scale_geom& g = geom[si];
+    const bool two_stage = !(g.valid_h == h && g.valid_w == w);
+    p->two_stage[si] = two_stage;
+    p->identity[si] = 0;   // both the x8 and the stage-2 source are interpolated
+    if (two_stage) p->stage1[si] = resize_form(1.0 / 8.0, false, g.valid_w, 1, false);
+    // rows per tile: every scale's source window fits the LDS rows
+    ty = fit_rows(ty, two_stage ? 1.0 / ((double)h / g.valid_h) : 1.0 / 8.0, p->identity[si]);
+  }
+  p->acc_ty = ty;
+  p->cc_lds = (long long)h * w <= CC_LDS_MAX;
+  p->cc_rows = std::max(1, CC_CHUNK / w);
+  p->cc_chunks = (h + p->cc_rows - 1) / p->cc_rows;
+}
+
+extern "C" int isl_debug_hand_post_plan(int h, int w, int nscales, const isl_scale_geom* geom,
+                                        isl_hand_post_plan* out) {
+  if (h <= 0 || w <= 0 || !out || !plan_geom_ok(nscales, geom))
+    return post_fail(ISL_E_ARG, "isl_debug_hand_post_plan: bad argument");
+  hand_post_plan(h, w, nscales, geom, out);
+  return ISL_OK;
+}
+
 // the kernels of one hand post (hand.py:51-74) on stream s, scratch at base
 // (hand_post_bytes); heat planes of scale si at d_heat[si] (NULL: the arena output)
 static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, const isl_scale_geom* geom,
@@ -3633,7 +3744,9 @@ static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, cons
   const size_t avg_bytes = (size_t)n * nparts * P * 8, mask_bytes = (size_t)n * nparts * h * words * 8;
   const size_t par_bytes = (size_t)n * nparts * P * 4, val_bytes = (size_t)n * nparts * P * 8;
   const size_t st_bytes = (size_t)n * nparts * sizeof(CcStats);
-  const int cc_rows = std::max(1, CC_CHUNK / w), cc_chunks = (h + cc_rows - 1) / cc_rows;
+  isl_hand_post_plan plan;   // the resize forms, the rows per tile and the component path
+  hand_post_plan(h, w, nscales, geom, &plan);
+  const int cc_rows = plan.cc_rows, cc_chunks = plan.cc_chunks;
   double* avg = (double*)base;
   float* mid = (float*)(base + up(avg_bytes));
   unsigned long long* mask = (unsigned long long*)((char*)mid + up(mid_bytes));
@@ -3646,7 +3759,7 @@ static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, cons
   const float div_f = (float)nscales;
   MapSrcN fin;                        // per scale: the resize that lands on the crop
   float* midp = mid;
-  int ty = RA_TY;
+  const int ty = plan.acc_ty;
   for (int si = 0; si < nscales; ++si) {
     const isl_scale_geom& g = geom[si];
     const int h8 = g.net_h / 8, w8 = g.net_w / 8;
@@ -3655,10 +3768,10 @@ static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, cons
     if (rc) return rc;
     lh.dh = h8 * 8; lh.dw = w8 * 8; lh.scy = lh.scx = 1.0 / 8.0; lh.cn = nch; lh.identity = 0;
     MapSrc fh = lh;
-    if (!(g.valid_h == h && g.valid_w == w)) {
+    if (plan.two_stage[si]) {
       const float* mid_s = midp;
       if (mid_pre && mid_pre[si]) mid_s = mid_pre[si];   // stage 1 done for the whole crop batch
-      else if ((rc = launch_resize(lh, n, nparts, g.valid_h, g.valid_w, 1, 1.f, midp, s))) return rc;
+      else if ((rc = launch_resize(lh, n, nparts, g.valid_h, g.valid_w, 1, 1.f, midp, s, plan.stage1[si]))) return rc;
       fh.base = mid_s; fh.xs = 1; fh.ys = g.valid_w; fh.cstr = (long long)g.valid_h * g.valid_w;
       fh.fs = (long long)nparts * g.valid_h * g.valid_w;
       fh.cshift = 30; fh.cbig = 0;
@@ -3668,8 +3781,9 @@ static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, cons
       midp += (size_t)n * g.valid_h * g.valid_w * nparts;
     }
     fin.m[si] = fh;
-    if (!fh.identity)   // rows per tile: every scale's source window fits the LDS rows
-      while (ty > 1 && (ty - 1) * fh.scy + 5.0 > (double)RS_MAXR) --ty;
+    // (the kernel traps on a taller tile than a scale's window allows)
+    if ((bool)fh.identity != (bool)plan.identity[si] || ty < 1 || fit_rows(ty, fh.scy, fh.identity) != ty)
+      return post_fail(ISL_E_STATE, "hand post: the plan's rows per tile do not fit a scale");
   }
   {
     const long long ty_tiles = (h + ty - 1) / ty;
@@ -3690,7 +3804,7 @@ static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, cons
       if (flip[c0 + c]) f.bits[c >> 6] |= 1ull << (c & 63);
     return f;
   };
-  if (h * w <= CC_LDS_MAX) {
+  if (plan.cc_lds) {
     static bool attr = false;
     if (!attr) {
       PHIP(hipFuncSetAttribute((const void*)hand_cc_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3849,7 +3963,9 @@ extern "C" int isl_hand_post_crops_ex(isl_net* net, int n, const int32_t* crop_w
         if (rc) return rc;
         lh.dh = h8 * 8; lh.dw = w8 * 8; lh.scy = lh.scx = 1.0 / 8.0; lh.cn = 22; lh.identity = 0;
         mid_all[si] = (float*)(base + off[si] - 1);
-        if ((rc = launch_resize(lh, n, 21, g.valid_h, g.valid_w, 1, 1.f, mid_all[si], s))) return rc;
+        if ((rc = launch_resize(lh, n, 21, g.valid_h, g.valid_w, 1, 1.f, mid_all[si], s,
+                                resize_form(lh.scy, false, g.valid_w, 1, false))))
+          return rc;
       }
     }
   }

@@ -127,7 +127,7 @@ EXPORTS = ["isl_abi_version", "isl_last_error", "isl_net_create", "isl_net_destr
            "isl_body_post_opts", "isl_hand_post_opts", "isl_hand_post_crops_opts",
            "isl_net_preprocess_crops_flip", "isl_hand_post_ex", "isl_hand_post_crops_ex", "isl_augment",
            "isl_draw", "isl_sign_train_opts_default", "isl_sign_grad_workspace", "isl_sign_grad",
-           "isl_debug_conv3x3", "isl_debug_conv"]
+           "isl_debug_conv3x3", "isl_debug_conv", "isl_debug_body_post_plan", "isl_debug_hand_post_plan"]
 
 
 class IslCaps(ctypes.Structure):
@@ -276,6 +276,69 @@ def debug_conv(x, weight, bias, slope=None, *, act="none", kernel="x3", f16=Fals
     return DebugConvResult(y, pooled, r)
 
 
+PLAN_SCALES = 8
+BLUR_BRANCHES = ("MULTI_F64", "FUSED_LIVE", "BAND_LIVE", "DENSE")      # enum isl_blur_branch
+
+
+class IslResizePlan(ctypes.Structure):
+    """isl_resize_plan (include/islpose.h): one launch of the separable resize."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("launched", "ty", "cols", "v4", "bm", "identity")]
+
+
+class IslBodyPostPlan(ctypes.Structure):
+    """isl_body_post_plan (include/islpose.h)."""
+    _fields_ = ([(n, ctypes.c_int32) for n in
+                 ("multi", "two_stage", "fused", "fuse2", "wide", "skip2", "blur", "blur_bandmax", "acc_ty",
+                  "stage2_ty", "limb_z", "env_fused_blur", "env_fused_wide", "env_blur_list", "env_blur_bands",
+                  "env_resize_skip", "env_resize_v4", "env_blur_exact")] +
+                [("scale_two_stage", ctypes.c_int32 * PLAN_SCALES), ("stage1", IslResizePlan * PLAN_SCALES),
+                 ("final_rs", IslResizePlan * PLAN_SCALES), ("reserved", ctypes.c_int32 * 6)])
+
+
+class IslHandPostPlan(ctypes.Structure):
+    """isl_hand_post_plan (include/islpose.h)."""
+    _fields_ = [("two_stage", ctypes.c_int32 * PLAN_SCALES), ("identity", ctypes.c_int32 * PLAN_SCALES),
+                ("stage1", IslResizePlan * PLAN_SCALES), ("acc_ty", ctypes.c_int32), ("cc_lds", ctypes.c_int32),
+                ("cc_rows", ctypes.c_int32), ("cc_chunks", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)]
+
+
+def _resize_dict(r):
+    return {n: int(getattr(r, n)) for n, _ in IslResizePlan._fields_}
+
+
+def _geom_array(geoms):
+    return (IslScaleGeom * max(len(geoms), 1))(*[IslScaleGeom(*[int(v) for v in g]) for g in geoms])
+
+
+def body_post_plan(kind, n, H, W, geoms):
+    """isl_debug_body_post_plan as a dict: the host-side choices isl_body_post_opts makes for n
+    frames of H x W with the scale geometries `geoms` [(net_h, net_w, valid_h, valid_w)] and the
+    environment switches as they stand now.  `blur` is one of BLUR_BRANCHES; stage1 / final are
+    per-scale lists of resize dicts (launched, ty, cols, v4, bm, identity).  No device work."""
+    p = IslBodyPostPlan()
+    check(lib().isl_debug_body_post_plan(int(kind), int(n), int(H), int(W), len(geoms), _geom_array(geoms),
+                                         ctypes.byref(p)), "isl_debug_body_post_plan")
+    out = {name: int(getattr(p, name)) for name, t in IslBodyPostPlan._fields_ if t is ctypes.c_int32}
+    out["blur"] = BLUR_BRANCHES[p.blur]
+    out["scale_two_stage"] = [int(p.scale_two_stage[i]) for i in range(len(geoms))]
+    out["stage1"] = [_resize_dict(p.stage1[i]) for i in range(len(geoms))]
+    out["final"] = [_resize_dict(p.final_rs[i]) for i in range(len(geoms))]
+    return out
+
+
+def hand_post_plan(h, w, geoms):
+    """isl_debug_hand_post_plan as a dict: per scale two_stage, identity and the stage-1 resize
+    dict; acc_ty (resize_acc_kernel's rows per tile); cc_lds (1: the single-workgroup component
+    path, 0: the large-plane chain) with cc_rows / cc_chunks.  No device work."""
+    p = IslHandPostPlan()
+    check(lib().isl_debug_hand_post_plan(int(h), int(w), len(geoms), _geom_array(geoms), ctypes.byref(p)),
+          "isl_debug_hand_post_plan")
+    k = len(geoms)
+    return {"two_stage": [int(p.two_stage[i]) for i in range(k)], "identity": [int(p.identity[i]) for i in range(k)],
+            "stage1": [_resize_dict(p.stage1[i]) for i in range(k)], "acc_ty": int(p.acc_ty),
+            "cc_lds": int(p.cc_lds), "cc_rows": int(p.cc_rows), "cc_chunks": int(p.cc_chunks)}
+
+
 def post_opts_struct(opts: dict) -> IslPostOpts:
     """check_post_opts' dict -> the isl_post_opts the *_opts entry points take."""
     return IslPostOpts(opts["thre1"], opts["thre2"], opts["hand_thre"], opts["max_people"])
@@ -358,6 +421,10 @@ def lib():
     L.isl_debug_conv3x3.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]
     L.isl_debug_conv.argtypes = [ctypes.POINTER(IslDebugConvDesc), vp, vp, vp, vp, vp, vp,
                                  ctypes.POINTER(IslDebugConvResult)]
+    L.isl_debug_body_post_plan.argtypes = [i32, i32, i32, i32, i32, ctypes.POINTER(IslScaleGeom),
+                                           ctypes.POINTER(IslBodyPostPlan)]
+    L.isl_debug_hand_post_plan.argtypes = [i32, i32, i32, ctypes.POINTER(IslScaleGeom),
+                                           ctypes.POINTER(IslHandPostPlan)]
     for name in EXPORTS[2:]:
         getattr(L, name).restype = i32
     if L.isl_abi_version() != 1:
