@@ -9,7 +9,7 @@ OUT      := $(PKG)/islpose/libislpose.so
 # operation order bit-for-bit, which forbids fused multiply-adds.
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Iinclude -I$(CSRC) \
             -Wall -Wno-unused-function -Wno-unused-variable -Wno-unused-lambda-capture
-SRCS     := $(CSRC)/conv.hip $(CSRC)/conv_x3.hip $(CSRC)/conv_c12.hip $(CSRC)/wino_f16.hip $(CSRC)/wino.hip $(CSRC)/ops.hip $(CSRC)/post.hip $(CSRC)/sign.hip $(CSRC)/sign_train.hip $(CSRC)/augment.hip $(CSRC)/draw.hip $(CSRC)/pack.cpp $(CSRC)/runtime.cpp
+SRCS     := $(CSRC)/conv.hip $(CSRC)/conv_x3.hip $(CSRC)/conv_c12.hip $(CSRC)/wino_f16.hip $(CSRC)/wino.hip $(CSRC)/ops.hip $(CSRC)/post.hip $(CSRC)/sign.hip $(CSRC)/sign_train.hip $(CSRC)/augment.hip $(CSRC)/draw.hip $(CSRC)/pack.cpp $(CSRC)/x3_select.cpp $(CSRC)/runtime.cpp
 OBJS     := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 # development objects (tools/convbench): the product sources plus the rejected split-fp16
 # Winograd kernel and the s_memtime stamp variant, compiled with -DISLPOSE_DEV
@@ -18,14 +18,19 @@ DEV_OBJS := $(patsubst $(CSRC)/%,build_dev/%.o,$(DEV_SRCS))
 
 all: $(OUT)
 
-build/%.o: $(CSRC)/% $(CSRC)/internal.h $(CSRC)/pack.h $(CSRC)/sign_common.h include/islpose.h
+HDRS     := $(CSRC)/internal.h $(CSRC)/x3_select.h $(CSRC)/pack.h $(CSRC)/sign_common.h include/islpose.h
+
+# (x3_instances.h: the instance table of the split-fp16 kernels and its host-side copy)
+build/conv_x3.hip.o build/x3_select.cpp.o build_dev/conv_x3.hip.o build_dev/x3_select.cpp.o: $(CSRC)/x3_instances.h
+
+build/%.o: $(CSRC)/% $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 $(OUT): $(OBJS)
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,-z,defs -o $@ $(OBJS)
 
-build_dev/%.o: $(CSRC)/% $(CSRC)/internal.h $(CSRC)/pack.h $(CSRC)/sign_common.h include/islpose.h
+build_dev/%.o: $(CSRC)/% $(HDRS)
 	@mkdir -p build_dev
 	$(HIPCC) $(HIPFLAGS) -DISLPOSE_DEV -x hip -c $< -o $@
 
@@ -45,3 +50,8 @@ tools/convbench: tools/convbench.cpp $(DEV_OBJS)
 # digests of the weight packs on the CPU (tests/test_pack.py): host compiler only, no device
 tools/pack_digest: tools/pack_digest.cpp $(CSRC)/pack.cpp $(CSRC)/pack.h
 	$(HOSTCXX) -O2 -std=c++17 -ffp-contract=off -Wall -I$(CSRC) tools/pack_digest.cpp $(CSRC)/pack.cpp -o $@
+
+# what launch_conv_x3 would run for a launch, and the sweep that holds the instance table closed
+# under the decision (tests/test_x3_select.py): host compiler only, no device
+tools/x3_choice: tools/x3_choice.cpp $(CSRC)/x3_select.cpp $(CSRC)/x3_select.h $(CSRC)/x3_instances.h
+	$(HOSTCXX) -O2 -std=c++17 -ffp-contract=off -Wall -I$(CSRC) tools/x3_choice.cpp $(CSRC)/x3_select.cpp -o $@

@@ -549,7 +549,7 @@ typedef struct {
 } isl_debug_conv_desc;
 
 typedef struct {
-  int32_t variant;       /* x3_last_variant() (x3, rgb); for wino2 the code the runtime gives  */
+  int32_t variant;       /* the launch's variant code (x3, rgb); for wino2 the code the runtime gives  */
                          /* launch_wino_f16 (a constant: that launcher has no variants and is  */
                          /* called directly); 0 for direct / wino                              */
   int32_t range_flag;    /* the launch's range flag as a value                                */

@@ -86,6 +86,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
+#include <vector>
 
 #include "internal.h"
 
@@ -326,11 +327,6 @@ __device__ __forceinline__ void x3_reduce_item(const X3Args& a, int n, int cc, i
   if (bad) atomicOr(a.range_flag, 1);
 }
 
-// input segment capacity in pixels for a BPX-pixel tile (host: tile_pixels)
-constexpr int x3_segmax(int bpx) { return bpx + 64; }
-// capacity of the row-union run (VAR 512): 2 x (1536 + 4 x 857) x 16 B = 155 KiB of LDS
-// with the 128-channel 3x3 weight slabs
-constexpr int x3_segu_max() { return 856; }
 
 template <int KS, int WAVES_M, int WAVES_N, int WM, int WN, int VAR, int OCC>
 __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1), OCC) conv_x3_f16(X3Args a) {
@@ -1576,15 +1572,6 @@ __global__ void __launch_bounds__(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1),
 // is then bound by its 64-channel fp32 output write (~4.1 TB/s of HBM traffic).  4 waves,
 // 64co x 64px each.
 // ---------------------------------------------------------------------------
-constexpr int RGB_BCO = 64, RGB_TILE = 256;
-
-// fp16 products per MAC a launch executes: three (fp32-accurate), one under ISL_PREC_FP16
-static double x3_products(const ConvLaunch& c) { return c.f16 ? 1.0 : 3.0; }
-
-// the variant of the last conv_x3 / conv_x3_rgb launch of this thread (x3_last_variant)
-static thread_local int t_last_variant = 0;
-int x3_last_variant() { return t_last_variant; }
-
 // F16 (ISL_PREC_FP16): one-term products -- hi-only filters [kk][h][64][8] (pack_hi_only of pack_x3_rgb) and an
 // im2col tile of the hi halves alone.  O16 (ISL_ACT_FP16, with F16): the fp32 net input as ever, the
 // output stored as fp16 (x3_store4h) after the range check on the fp32 value
@@ -1712,12 +1699,10 @@ __global__ void __launch_bounds__(RGB_BPX, 1) conv_x3_rgb(X3Args a) {
   if (bad) atomicOr(a.range_flag, 1);
 }
 
-bool x3_rgb_fits(const ConvLaunch& c) {
-  return c.ks == 3 && c.cin_chunks == 1 && c.cout <= RGB_BCO && c.in_pad >= 1 && !c.hpool;
-}
-
 hipError_t launch_conv_x3_rgb(const ConvLaunch& c, hipStream_t s) {
-  if (!x3_rgb_fits(c) || !c.wx3 || !c.range_flag || ((c.in_cs | c.out_cs | c.out_coff | c.in_coff) & 7)) {
+  const X3Choice ch = x3_choose_rgb(c);
+  if (ch.family != X3Choice::RGB) { set_error(ch.error); return hipErrorInvalidValue; }
+  if (!c.wx3 || !c.range_flag || ((c.in_cs | c.out_cs | c.out_coff | c.in_coff) & 7)) {
     set_error("conv_x3_rgb: needs a 3x3 layer with one input chunk, <= 64 outputs and rgb-packed weights");
     return hipErrorInvalidValue;
   }
@@ -1726,10 +1711,6 @@ hipError_t launch_conv_x3_rgb(const ConvLaunch& c, hipStream_t s) {
   a.out_chs = (long long)(c.H + 2 * c.out_pad) * (c.W + 2 * c.out_pad) * 8;
   a.in_fs = a.in_chs * (c.in_cs / 8);
   a.out_fs = a.out_chs * (c.out_cs / 8);
-  if (c.act16 && (!c.f16 || c.out32)) {
-    set_error("conv_x3_rgb: fp16 activation storage needs the one-term form (and is no net output)");
-    return hipErrorInvalidValue;
-  }
   a.in = c.in + (c.in_coff / 8) * a.in_chs;
   a.out = c.act16 ? (float*)((_Float16*)c.out + (c.out_coff / 8) * a.out_chs) : c.out + (c.out_coff / 8) * a.out_chs;
   a.wpk = (const f16x8*)c.wx3; a.bias = c.bias; a.slope = c.slope;
@@ -1738,9 +1719,7 @@ hipError_t launch_conv_x3_rgb(const ConvLaunch& c, hipStream_t s) {
   a.in_pad = c.in_pad; a.out_pad = c.out_pad;
   a.H = c.H; a.W = c.W; a.cin_chunks = 1; a.pairs = 1; a.cout = c.cout;
   a.co_tiles = 1;
-  // 256-pixel blocks: 3 % faster than 512 (more blocks resident per CU), 128 lost 16 %
-  // (tools/archive/gpu_rgb_bpx.sh)
-  constexpr int bpx = RGB_TILE;
+  constexpr int bpx = RGB_TILE;   // (x3_choose_rgb: the one tile built)
   a.px_tiles = (c.H * c.W + bpx - 1) / bpx;
   a.tpx = bpx;
   a.act = c.act;
@@ -1749,15 +1728,10 @@ hipError_t launch_conv_x3_rgb(const ConvLaunch& c, hipStream_t s) {
   const long long nb = (long long)c.n * a.px_tiles;
   if (nb <= 0 || nb > 0x7fffffff) { set_error("conv_x3_rgb: bad grid"); return hipErrorInvalidValue; }
   a.nblocks = (int)nb;
-  t_last_variant = x3_variant_code(X3V_RGB | (c.f16 ? X3V_F16 : 0) | (c.act16 ? X3V_A16 : 0), 3, bpx, RGB_BCO);
   if (c.act16) hipLaunchKernelGGL((conv_x3_rgb<bpx, true, true>), dim3(a.nblocks), dim3(bpx), 0, s, a);
   else if (c.f16) hipLaunchKernelGGL((conv_x3_rgb<bpx, true>), dim3(a.nblocks), dim3(bpx), 0, s, a);
   else hipLaunchKernelGGL((conv_x3_rgb<bpx, false>), dim3(a.nblocks), dim3(bpx), 0, s, a);
   return hipGetLastError();
-}
-
-double conv_x3_rgb_mfma_flops(const ConvLaunch& c) {
-  return x3_products(c) * 2.0 * RGB_BCO * 32.0 * (double)((c.H * c.W + RGB_TILE - 1) / RGB_TILE) * RGB_TILE * c.n;
 }
 
 __global__ void __launch_bounds__(256) x3_splitk_reduce(X3Args a) {
@@ -1971,63 +1945,13 @@ __global__ void __launch_bounds__(512) conv_x3_wr(X3Args a) {
   if (bad) atomicOr(a.range_flag, 1);
 }
 
-// Tail tiles.  A chip-filling grid of full tiles takes ceil(blocks / CUs) rounds of one block per
-// CU, its last round often part-empty (Mode N's 92x164 layers: 1920 blocks, 7.5 rounds -> 8; the
-// layer time follows the rounds, tools/round_probe.py).  Where it pays by the estimate below, each
-// frame's first full_tiles tiles fill whole rounds and the rest of its pixels run as tail tiles of
-// ttpx pixels (a multiple of 128, so that the MFMA-skipping waves past the tile stay spread over
-// the SIMDs), dispatched after them.  The plan prices a tail block at 0.3 + 0.7 ttpx / tpx of a
-// full one; measured, a 256-pixel tail of the 512-pixel row union costs ~0.85 (its weight slabs,
-// staging and barriers stay: profiles/r05/r5tl), so only clear wins are taken (>= 0.25 round by
-// the estimate).  Every output keeps its MFMA sequence: same bits.
-// ISLPOSE_X3_TAIL=0: one tiling (A/B; read per launch).
-static int device_cus();
-static void x3_tail_plan(int n, int HW, X3Args& a) {
-  a.nb_full = a.full_tiles = a.tail_tiles = a.ttpx = 0;
-  const char* e = getenv("ISLPOSE_X3_TAIL");
-  if (e && e[0] == '0') return;
-  const long long cus = device_cus(), per = (long long)n * a.co_tiles;
-  const long long R0 = (per * a.px_tiles + cus - 1) / cus;
-  const int full_max = HW / a.tpx;
-  const long long Rf = per * full_max / cus;        // whole rounds the full tiles can fill
-  if (Rf < 1 || R0 < 2) return;
-  const int F = (int)(Rf * cus / per);
-  const long long NF = per * F;
-  if (F < 1 || NF % 8) return;                      // (each class is spread over the 8 XCDs)
-  const int rem = HW - F * a.tpx;
-  double best = (double)R0 - 0.25;
-  for (int t = 128; t < a.tpx; t += 128) {
-    const int TT = (rem + t - 1) / t;
-    const long long NT = per * TT;
-    const double est = (double)NF / cus + (double)((NT + cus - 1) / cus) * (0.3 + 0.7 * t / a.tpx);
-    if (est < best && NF + NT <= 0x7fffffff) {
-      best = est;
-      a.nb_full = (int)NF; a.full_tiles = F; a.tail_tiles = TT; a.ttpx = t;
-      a.nblocks = (int)(NF + NT);
-    }
-  }
-}
-
-// fp16 activation storage (VAR 1): the row union stages its plain input runs by LDS-DMA.
-// ISLPOSE_A16_DMA=0: through registers, as every other loop (A/B; read per launch).
-static bool x3_a16_dma() {
-  const char* e = getenv("ISLPOSE_A16_DMA");
-  return !(e && e[0] == '0');
-}
-
+// The argument fill and the checks of one conv_x3_f16 instance (x3_instances.h); c with the K-range
+// count of the choice (launch_conv_x3)
 template <int KS, int WAVES_M, int WAVES_N, int WM, int WN, int VAR, int OCC>
-static hipError_t launch_t(const ConvLaunch& c, hipStream_t s) {
+static hipError_t launch_t(const ConvLaunch& c, const X3Choice& ch, int cus, const X3Switches& sw, hipStream_t s) {
   constexpr int BCO = WAVES_M * WM * 32;
   constexpr int BPX = WAVES_N * WN * 32;
-  // (the fused pair's 512-channel tile does not fit the 4-bit tile field: it records BCO / 2,
-  // decode_variant doubles it back for VAR 16)
-  t_last_variant = x3_variant_code(VAR, KS, BPX, (VAR & 16) ? BCO / 2 : BCO);
   constexpr bool A16 = (VAR & X3V_A16) != 0;
-  // the variants without an fp16-storage form (x3_act16_ok: the runtime never plans them)
-  if constexpr (A16 && ((VAR & (2048 | 8192 | 16384 | 131072)) != 0 || (KS == 7 && WAVES_N == 3))) {
-    set_error("conv_x3: no fp16-storage form of this variant (x3_act16_ok)");
-    return hipErrorInvalidValue;
-  } else {
   if (A16 != (c.act16 != 0)) { set_error("conv_x3: fp16-storage variant mismatch"); return hipErrorInvalidValue; }
   if (c.out32 && (!A16 || c.hpool || (c.out32_cs & 7) || ((VAR & 16) != 0 && c.out32_cs < (c.cout7 + 7) / 8 * 8))) { set_error("conv_x3: fp32 output copy outside fp16 storage"); return hipErrorInvalidValue; }
   constexpr int P = KS / 2;
@@ -2072,11 +1996,7 @@ static hipError_t launch_t(const ConvLaunch& c, hipStream_t s) {
     set_error("conv_x3: fused-pair launch on a plain variant");
     return hipErrorInvalidValue;
   }
-#ifdef ISLPOSE_DEV
-  a.abl = getenv("ISLPOSE_X3_ABL") ? atoi(getenv("ISLPOSE_X3_ABL")) : 0;
-#else
-  a.abl = 0;
-#endif
+  a.abl = sw.abl;   // (development builds only: 0 elsewhere)
   if ((c.fold != nullptr) != ((VAR & 8192) != 0)) { set_error("conv_x3: fold variant mismatch"); return hipErrorInvalidValue; }
   if (c.vin != ((VAR & 32768) != 0)) { set_error("conv_x3: pooled-input variant mismatch"); return hipErrorInvalidValue; }
   a.out_chs = (long long)(c.H + 2 * c.out_pad) * (c.W + 2 * c.out_pad) * 8;
@@ -2091,7 +2011,9 @@ static hipError_t launch_t(const ConvLaunch& c, hipStream_t s) {
     a.out32_pad = c.out32_pad;
     a.out32_chs = (long long)(c.H + 2 * c.out32_pad) * (c.W + 2 * c.out32_pad) * 8;
     a.out32_fs = a.out32_chs * (c.out32_cs / 8);
-    a.xdma = x3_a16_dma() ? 1 : 0;
+    // the row union stages its plain input runs by LDS-DMA; ISLPOSE_A16_DMA=0: through registers,
+    // as every other loop (A/B)
+    a.xdma = sw.a16_dma ? 1 : 0;
   }
   a.wpk = (const f16x8*)c.wx3; a.bias = c.bias; a.slope = c.slope;
   a.range_flag = c.range_flag;
@@ -2120,7 +2042,11 @@ static hipError_t launch_t(const ConvLaunch& c, hipStream_t s) {
   const long long nb = (long long)c.n * a.px_tiles * a.co_tiles * (SPLIT ? a.ksplit : 1);
   if (nb <= 0 || nb > 0x7fffffff) { set_error("conv_x3: bad grid"); return hipErrorInvalidValue; }
   a.nblocks = (int)nb;
-  if constexpr (!SPLIT && !RANGED && !(VAR & 16) && BPX >= 256) x3_tail_plan(c.n, c.H * c.W, a);
+  if constexpr (!SPLIT && !RANGED && !(VAR & 16) && BPX >= 256) {
+    const X3Tail t = x3_tail_plan(c.n, c.H * c.W, a.co_tiles, a.px_tiles, a.tpx, a.nblocks, cus, sw);
+    a.nb_full = t.nb_full; a.full_tiles = t.full_tiles; a.tail_tiles = t.tail_tiles; a.ttpx = t.ttpx;
+    a.nblocks = t.nblocks;
+  }
   hipLaunchKernelGGL((conv_x3_f16<KS, WAVES_M, WAVES_N, WM, WN, VAR, OCC>), dim3(a.nblocks),
                      dim3(WAVES_M * WAVES_N * 64 * ((VAR & 32) ? 2 : 1)), 0, s, a);
   if constexpr (SPLIT) {
@@ -2133,22 +2059,9 @@ static hipError_t launch_t(const ConvLaunch& c, hipStream_t s) {
     if (c.fold_out) { set_error("conv_x3: fold_out without split-K across blocks"); return hipErrorInvalidValue; }
   }
   return hipGetLastError();
-  }
 }
 
-static bool x3_small_tiles() {
-  static const bool v = getenv("ISLPOSE_X3_TILES") && getenv("ISLPOSE_X3_TILES")[0] == 's';
-  return v;
-}
-
-// 0: no row union (A/B), 1: row union (default), 4: row union with s_memtime stamps
-// (development; needs ConvLaunch::dbg, set only by tools/convbench)
-static int x3_union_mode() {
-  static const int m = getenv("ISLPOSE_X3_UNION") ? atoi(getenv("ISLPOSE_X3_UNION")) : 1;
-  return m;
-}
-
-static int device_cus() {
+int device_cus() {
   static const int n = [] {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -2158,618 +2071,10 @@ static int device_cus() {
   return n;
 }
 
-// Canonical K ranges of a layer, from its shape alone (never the batch): the small
-// stage layers (<= 1024 pixels per frame: Mode R's 23x41 body stages, the 184 px hand
-// scale) sum their chunk pairs in S ranges, so that a batch-1 frame can spread them
-// over S blocks (split-K) and a large batch can keep them in one block, with the same
-// bits.  Every range is ceil(pairs / S) pairs long and non-empty.
-// Small grids (the 128-pixel family) with 128-channel tiles on two 64-channel blocks of 4
-// waves each (VAR 256): by default the 1x1 / 3x3 layers whose K ranges are split across
-// blocks (grids below one block per CU: batch-1 Mode R, +4 % frames/s), where doubling the
-// grid buys more than the second staging of the input costs; with one block per CU (Mode R
-// batch 32) it loses 10-20 % (profiles/r03/halfco_ab/).  Same bits either way.
-// ISLPOSE_X3_HALFCO=0 off, =1 every 128-channel launch of the family (read per launch; A/B).
-static bool x3_small7(const ConvLaunch& c);
-static bool x3_halfco(const ConvLaunch& c) {
-  if (c.ks > 7 || c.fold) return false;
-  if (c.ks == 7) return c.ksplit > 1 && c.ws && x3_small7(c);
-#ifdef ISLPOSE_DEV
-  // development build only (A/B of profiles/r03/halfco_ab/): =0 off, =1 every 128-channel
-  // launch of the family (measured slower at one block per CU, so not in the product)
-  const char* e = getenv("ISLPOSE_X3_HALFCO");
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '1') return true;
-#endif
-  return c.ks <= 3 && c.ksplit > 1 && c.ws;
-}
-
-// Small 7x7 grids (a frame's hand crops per call: one or two crops at the 46^2 - 92^2 hand
-// scales, or the 23^2 scale's across-block K ranges), under one 128-pixel block per CU: the
-// 128-channel tiles run as two 64-channel blocks on 64-pixel tiles (VAR 256, 4 waves of 32co x
-// 32px, two blocks per CU): 4x the blocks, each output the same MFMA sequence (same ranges, same
-// K order), so the same bits as the batched crops.  ISLPOSE_X3_SMALL7=0 off (A/B; per launch).
-static int x3_small7_mode() {
-  const char* e = getenv("ISLPOSE_X3_SMALL7");
-  return e ? atoi(e) : 2;
-}
-static bool x3_small7(const ConvLaunch& c) {
-  if (c.ks != 7 || c.bco != 128 || c.fold || c.vin || c.hpool) return false;
-  if (x3_small7_mode() == 0) return false;
-  const int tpx = tile_pixels(c, 128, x3_segmax(128));
-  const long long blocks = (long long)c.n * ((c.H * c.W + tpx - 1) / tpx) * std::max(1, c.ksplit);
-  return blocks < device_cus();
-}
-// ... with the operands two K steps ahead (VAR 128: a ring of three 28 KiB weight slabs, one
-// block per CU) where the 64-pixel grid still fits one block per CU: the 46^2 / 69^2 scales
-// of one crop 55 -> 48 us per layer; past one round (92^2: 266 blocks) the two resident
-// blocks of the plain loop win (profiles/r05/r5s7b/).  ISLPOSE_X3_SMALL7=1: never, 3: always.
-static bool x3_small7_deep(const ConvLaunch& c) {
-  const int m = x3_small7_mode();
-  if (m < 2) return false;
-  if (m >= 3) return true;
-  const int tpx = tile_pixels(c, 64, x3_segmax(64));
-  return (long long)c.n * ((c.H * c.W + tpx - 1) / tpx) * 2 * std::max(1, c.ksplit) <= device_cus();
-}
-
-// ... on 96-pixel tiles (6 waves of 32co x 32px, two steps ahead) where the 64-pixel grid takes
-// more than one round of one block per CU and the 96-pixel grid takes one: one crop at the
-// 92^2 (736 px) hand scale, 266 -> 178 blocks (the 64-pixel plain loop left 10 CUs with two
-// blocks, every layer waiting on them).  No K range is split: the same bits.
-// ISLPOSE_X3_S7W96=0 off (A/B; read per launch).
-static bool x3_small7_96(const ConvLaunch& c) {
-  const char* e = getenv("ISLPOSE_X3_S7W96");
-  if ((e && e[0] == '0') || x3_small7_mode() != 2 || c.ksplit > 1) return false;
-  const long long HW = (long long)c.H * c.W, cus = device_cus();
-  const int t64 = tile_pixels(c, 64, x3_segmax(64)), t96 = tile_pixels(c, 96, x3_segmax(96));
-  return c.n * ((HW + t64 - 1) / t64) * 2 > cus && c.n * ((HW + t96 - 1) / t96) * 2 <= cus;
-}
-
-// Small grids (the 128-pixel family) with two K groups per block (VAR 32, 16 waves: the first
-// and second half of the canonical K ranges side by side, one block per CU): every 128-channel
-// 1x1 / 3x3 launch whose K ranges run in one block (Mode R's 23x41 stage layers and conv4_x at
-// batch >= 32; 5-6 % faster than the one-group loops there, profiles/r04/r4b/).  The 96-channel
-// form (two groups of 6 waves of 32co x 64px) measured 7 % slower than the deep-prefetch loop on
-// the c96 stage layers and is not built.  The one-group form keeps both halves' sums and the
-// range's in registers (153 VGPRs: one 8-wave block per CU) where two groups hold one each (122:
-// 16 waves per CU).
-// ISLPOSE_X3_G2=0: the one-group loops (A/B; read per launch).
-static bool x3_g2(const ConvLaunch& c) {
-  if (c.ks > 3 || c.bco != 128 || c.fold || c.vin || c.ksplit < 2 || c.ws) return false;
-  const char* e = getenv("ISLPOSE_X3_G2");
-  return !(e && e[0] == '0');
-}
-
-// Small grids whose K ranges run across blocks (batch-1 Mode R's 23x41 stage layers: 8 pixel
-// tiles x S ranges, far under one block per CU) on 64-pixel tiles: the 96-channel tiles as 6
-// waves of 32co x 32px (not 12 on 128 pixels), the half-channel blocks of the 128-channel tiles
-// (VAR 256) as 4 waves of 32co x 32px (not 4 of 64co x 32px on 128 pixels) -- twice the blocks,
-// each with half the MFMAs and staging per K step.  Each output sees the same MFMA sequence (same
-// ranges, same K order): same bits.  Batch-1 Mode R net 1.955 -> 1.828 ms (profiles/r04/r4ai/).
-// ISLPOSE_X3_PX64=0: the 128-pixel blocks, =1: the 96-channel tiles only (A/B; read per launch).
-static int x3_px64_mode() {
-  const char* e = getenv("ISLPOSE_X3_PX64");
-  return e ? atoi(e) : 2;
-}
-static bool x3_px64(const ConvLaunch& c) {
-  if (c.ks > 3 || c.bco != 96 || c.fold || c.vin || c.ksplit < 2 || !c.ws) return false;
-  return x3_px64_mode() >= 1;
-}
-
-// Small 3x3 grids without K ranges (batch-1 conv2_x / conv3_x: at most half a block per CU) on
-// half-channel blocks (VAR 256): twice the blocks; same MFMA sequence per output, same bits.
-// Batch-1 Mode R net 1.828 -> 1.817 ms; the 1x1 layers (the two-launch Mconv6) measured slower
-// and the deep-prefetch form level (profiles/r04/r4ai/).  ISLPOSE_X3_HALFSMALL=0 off (A/B).
-static bool x3_halfsmall(const ConvLaunch& c) {
-  const char* e = getenv("ISLPOSE_X3_HALFSMALL");
-  if ((e && e[0] == '0') || c.ks != 3 || c.bco != 128 || c.fold || c.vin || c.ksplit > 1) return false;
-  const int tpx = tile_pixels(c, 128, x3_segmax(128));
-  const long long blocks = (long long)c.n * ((c.H * c.W + tpx - 1) / tpx) * ((c.cout + c.bco - 1) / c.bco);
-  return 2 * blocks <= device_cus();
-}
-
-// Small grids (the 128-pixel family) with the inputs and weights prefetched two K steps
-// ahead (VAR 128): by default the 3x3 layers whose grid has at most one block per CU and
-// whose K ranges (if any) run in one block -- Mode R's 23x41 stage layers at batch 32, -5 to
-// -12 % per layer in the net (profiles/r03/deep_ab/).  Its ring of three weight slabs (98 KiB)
-// allows one block per CU, so grids with more blocks lose the second resident block (conv4_x
-// at batch 32: +12-16 %), and the 1x1 layers lost 25-30 %.  ISLPOSE_X3_DEEP=0 off, =1 every
-// 1x1 / 3x3 launch of the family, across-block ranges included (A/B; read per launch).
-static bool x3_deep(const ConvLaunch& c) {
-  const char* e = getenv("ISLPOSE_X3_DEEP");
-  if (c.fold || c.vin || (c.bco != 128 && c.bco != 96) || c.ks > 3) return false;
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '1') return true;
-  if (c.ks != 3 || (c.ksplit > 1 && c.ws)) return false;
-  const int tpx = tile_pixels(c, 128, x3_segmax(128));
-  const long long blocks = (long long)c.n * ((c.H * c.W + tpx - 1) / tpx) * ((c.cout + c.bco - 1) / c.bco);
-  return blocks <= device_cus();
-}
-
-// Small grids (the 128-pixel family) with two chunk pairs per K step (VAR 4096): a step's
-// MFMAs double against its barrier and its L2 round trip.  Only for layers with canonical K
-// ranges (they never run the big-tile kernels, whose one-pair order the other layers must
-// keep for batch-invariant bits), an even number of pairs in every range, and one channel
-// tile (c512 lost 7 %).  Per layer (tools/convbench, 23x41 at batch 32) c128 -3 %, c96 -8 %,
-// c384 / c288 -1.5 % time, but the whole of Mode R moved by +-1 % (batch 32 +0.5 %, batch 1
-// -1.2 %, profiles/r03/pps2_ab/), so it is off by default.  ISLPOSE_X3_PPS2=1: on (A/B; read
-// per launch).
-static int x3_canonical_ranges(const ConvLaunch& c);
-#ifdef ISLPOSE_DEV
-static bool x3_pps2(const ConvLaunch& c) {
-  // the fold A/B (ISLPOSE_X3_FOLD=1) runs its consumers on one-pair steps, so every layer of a
-  // frame keeps one order at every batch size only with PPS2 off there
-  const char* e = getenv("ISLPOSE_X3_PPS2");
-  const char* f = getenv("ISLPOSE_X3_FOLD");
-  if (!(e && e[0] == '1') || (f && f[0] == '1') || c.ks > 3 || c.vin || (c.bco != 128 && c.bco != 96) ||
-      c.cout > c.bco)
-    return false;
-  const int S = x3_canonical_ranges(c), pairs = (c.cin_chunks + 1) / 2;
-  if (S < 2 || c.ksplit != S) return false;
-  const int pps = (pairs + S - 1) / S;
-  return pairs % 2 == 0 && pps % 2 == 0;
-}
-#else
-static bool x3_pps2(const ConvLaunch&) { return false; }   // rejected (profiles/r03/pps2_ab/): dev build only
-#endif
-
-static int x3_canonical_ranges(const ConvLaunch& c) {
-  // 3x3 / 7x7 layers: ranges of >= 2 chunk pairs; 1x1 layers: >= 4 pairs (64 channels), so
-  // that a range of an Mconv7 is one wave's share of the fused pair (VAR 16) and the two
-  // executions of the pair give the same bits
-  const int pairs = (c.cin_chunks + 1) / 2, per = c.ks == 1 ? 4 : 2;
-  if (!c.allow_split || c.H * c.W > 1024 || pairs < 2 * per) return 1;
-  int S = std::min(8, pairs / per);
-  while (S > 1 && (S - 1) * ((pairs + S - 1) / S) >= pairs) --S;
-  return S;
-}
-
-// Tile families.  3x3 / 1x1 layers: 512-pixel tiles (16 waves per block, one
-// block per CU): the weight slab of a K step is then shared by 4x the pixels,
-// which cut the L2->LDS bytes per FLOP ~2x and measured +10 % over the 128-pixel
-// tiles (r01); 16 rather than 8 waves for the narrow (96/64/32-channel) tiles
-// +2-9 %.  7x7 layers keep 128-pixel tiles (their slab is 2.3x larger), and so do
-// layers with canonical K ranges (their second accumulator set needs the 128-pixel
-// family's register budget).  512-pixel tiles are used only when they fill the
-// chip: a layer with fewer such blocks than CUs runs ~2x faster on the 128-pixel,
-// 4-wave family (tools/archive/gpu_tiles.sh).
-static bool x3_union(const ConvLaunch& c);
-
-// 64-channel 3x3 layers off the row union (full-resolution conv1_2 / hand conv1_2: 12 K
-// steps) run 256-pixel blocks of 8 waves (64co x 32px each), two blocks per CU, so that one
-// block's prologue and epilogue overlap the other's K loop: -4 to -5 % against the 16-wave
-// 512-pixel block (tools/archive/gpu_mid.sh; the 128-channel layers stay on 512 pixels, where every
-// 256-pixel shape lost 4-7 %).  ISLPOSE_X3_HALF64=0: the 512-pixel block (A/B).
-static bool x3_half64(const ConvLaunch& c) {
-  static const bool on = !(getenv("ISLPOSE_X3_HALF64") && getenv("ISLPOSE_X3_HALF64")[0] == '0');
-  return on && c.ks == 3 && c.bco == 64 && !x3_union(c);
-}
-
-static int x3_big_bpx(const ConvLaunch& c) { return (c.ks == 1 && c.bco == 256) || x3_half64(c) ? 256 : 512; }
-
-static bool x3_big_tiles(const ConvLaunch& c) {
-  if (c.ks > 3 || x3_small_tiles() || x3_canonical_ranges(c) > 1) return false;
-  const int bpx = x3_big_bpx(c), tpx = tile_pixels(c, bpx, x3_segmax(bpx));
-  const long long px_tiles = (c.H * c.W + tpx - 1) / tpx;
-  return (long long)c.n * px_tiles * ((c.cout + c.bco - 1) / c.bco) >= device_cus();
-}
-
-// 1x1 layers with 256k output channels and an even number of chunk pairs (Mconv6 of
-// every stage: 384/288 -> 512/256) also pack their split filters for 256-channel
-// tiles.  On big grids they run 16 waves of 64co x 64px over 256 pixels with two chunk
-// pairs per K step (VAR 4096: 24 MFMAs per wave between barriers instead of 12, and
-// the input read for half as many channel tiles): +7-12 % (tools/archive/gpu_k1.sh).  Small
-// grids (K ranges, the 128-pixel family) keep the 128-channel packing: 256-channel
-// tiles there halve the blocks and lost 30 %.
-bool x3_wide1_layer(int ks, int cout, int cin_phys) {
-  return ks == 1 && cout % 256 == 0 && ((cin_phys / 8 + 1) / 2) % 2 == 0;
-}
-
-bool x3_wide1(const ConvLaunch& c) {
-  return c.bco == 256 && x3_wide1_layer(c.ks, c.cout, c.cin_chunks * 8) && x3_big_tiles(c);
-}
-
-// 7x7 layers on 256-pixel tiles (8 waves of 64co x 64px, 156 KiB of LDS) or on
-// 128-pixel tiles (8 waves of 64co x 32px): one block per CU either way (a step's
-// weight slab is 56 KiB).  The 256-pixel block does twice the work for ~1.72x the
-// time of a 128-pixel block (half the weight bytes per MFMA), so the choice is per
-// launch, by grid quantisation: rounds of one block per CU, a 256-pixel block costing
-// X3_WIDE7_COST 128-pixel blocks.  Both pack the weights for 128-channel tiles.
-// Round 6 re-measured the three forms on the hand's batch-32 grids of C3 (op tables,
-// profiles/r06/w7ab/): 69^2 x 32 ran 11.93 / 10.89 / 11.36 ms over its twenty 7x7 stage
-// layers on 128 / 256 / 384 pixels (5 / 3 / 2 rounds), i.e. 1.52 and 2.38 128-pixel rounds
-// per round; with the round-2 costs (1.74, 2.58; tools/archive/gpu_wide7.sh, gpu_w384.sh)
-// the estimate kept 69^2 on 128 pixels.  92^2 (384) and 46^2 (384) choose as before.
-constexpr double X3_WIDE7_COST = 1.52;
-// a round of 384-pixel blocks (12 waves, one input buffer)
-constexpr double X3_W384_COST = 2.38;
-
-static int x3_wide7_mode() {   // ISLPOSE_X3_WIDE7: 0 never, 1 always (A/B), default by the estimate
-  static const int m = getenv("ISLPOSE_X3_WIDE7") ? atoi(getenv("ISLPOSE_X3_WIDE7")) : 2;
-  return m;
-}
-
-// pixels per 7x7 tile (128, 256 or 384), chosen per launch by grid quantisation: rounds
-// of one block per CU, a round of 256- / 384-pixel blocks costing X3_WIDE7_COST /
-// X3_W384_COST of a 128-pixel round.  ISLPOSE_X3_WIDE7=0|1|3 forces 128 / 256 / 384 (A/B).
-static int x3_7x7_bpx(const ConvLaunch& c) {
-  if (c.ks != 7 || c.bco != 128 || x3_small_tiles() || x3_canonical_ranges(c) > 1) return 128;
-  const int mode = x3_wide7_mode();
-  if (mode != 2) return mode == 1 ? 256 : mode == 3 ? 384 : 128;
-  const long long HW = (long long)c.H * c.W, co = (c.cout + 127) / 128, cus = device_cus();
-  int best = 128;
-  double best_t = 0.0;
-  for (int bpx : {128, 256, 384}) {
-    const int t = tile_pixels(c, bpx, x3_segmax(bpx));
-    const long long b = c.n * ((HW + t - 1) / t) * co;
-    const double cost = bpx == 128 ? 1.0 : bpx == 256 ? X3_WIDE7_COST : X3_W384_COST;
-    const double tt = (double)((b + cus - 1) / cus) * cost;
-    if (bpx == 128 || tt < best_t) { best = bpx; best_t = tt; }
-  }
-  return best;
-}
-
-static bool x3_wide7(const ConvLaunch& c) { return x3_7x7_bpx(c) == 256; }
-
-// 7x7 on 384-pixel tiles (VAR 65536, one input buffer)
-static bool x3_wide7_384(const ConvLaunch& c) { return x3_7x7_bpx(c) == 384; }
-
-// Row-union staging (VAR 512) when the longest union run of any 512-pixel tile fits.
-// longest row-union run (pixels) over the 512-pixel tiles of a layer
-static int x3_union_run(const ConvLaunch& c) {
-  const int P = c.ks / 2, Wi = c.W + 2 * c.in_pad, HW = c.H * c.W;
-  const int tpx = tile_pixels(c, 512, x3_segmax(512));
-  int span = 0;
-  for (int m0 = 0; m0 < HW; m0 += tpx) {
-    const int ml = std::min(m0 + tpx, HW) - 1;
-    span = std::max(span, (ml / c.W - m0 / c.W) * Wi + (ml % c.W - m0 % c.W));
-  }
-  return span + 2 * P * Wi + 2 * P + 1;
-}
-
-static bool x3_union(const ConvLaunch& c) {
-  if (x3_union_mode() == 0 || c.ks != 3 || x3_small_tiles() || x3_canonical_ranges(c) > 1) return false;
-  return x3_union_run(c) <= x3_segu_max();
-}
-
-// The row union on v_mfma_f32_16x16x32_f16 (VAR 131072) for 128-channel tiles with an even
-// number of chunk pairs.  ISLPOSE_X3_M16=0|1 (read per launch: A/B in one process).
-#ifdef ISLPOSE_DEV
-static bool x3_m16(const ConvLaunch& c) {
-  const char* e = getenv("ISLPOSE_X3_M16");
-  const bool on = e && e[0] == '1';
-  return on && c.ks == 3 && c.bco == 128 && ((c.cin_chunks + 1) / 2) % 2 == 0;
-}
-#else
-static bool x3_m16(const ConvLaunch&) { return false; }    // rejected (profiles/r03/m16_ab/): dev build only
-#endif
-
-// K-range plan of a launch on the 128-pixel family: S ranges, computed across S blocks
-// per tile (split-K, partials through the workspace) when the plain grid has fewer
-// blocks than CUs, else in one block (tools/archive/gpu_across.sh: across wins 10-50 % at
-// 64-160 blocks, in-block wins 20-70 % at 256-1024 -- same bits either way).  With isl_net_set_split_k(net, 2) (latency
-// mode) layers without canonical ranges also split when their grid is that small --
-// an adaptive S that depends on the batch, so those layers' bits then do too.
-struct X3Ranges {
-  int S = 1;
-  bool across_blocks = false;
-};
-
-static X3Ranges x3_ranges(const ConvLaunch& c) {
-  X3Ranges r;
-  if (x3_big_tiles(c) || x3_7x7_bpx(c) != 128) return r;
-  const int tpx = tile_pixels(c, 128, x3_segmax(128));
-  const long long blocks = (long long)c.n * ((c.H * c.W + tpx - 1) / tpx) * ((c.cout + c.bco - 1) / c.bco);
-  const int cus = device_cus(), pairs = (c.cin_chunks + 1) / 2;
-  r.S = x3_canonical_ranges(c);
-  if (r.S > 1) {
-    static const int force = getenv("ISLPOSE_X3_ACROSS") ? atoi(getenv("ISLPOSE_X3_ACROSS")) : -1;   // A/B
-    r.across_blocks = force >= 0 ? force == 1 : blocks < cus;
-    return r;
-  }
-  if (c.allow_split == 2 && 2 * blocks <= cus && pairs >= 4) {
-    int S = (int)std::min<long long>({8, pairs / 2, (cus + blocks - 1) / blocks});
-    while (S > 1 && (S - 1) * ((pairs + S - 1) / S) >= pairs) --S;
-    r.S = S;
-    r.across_blocks = S > 1;
-  }
-  return r;
-}
-
-// FV: X3V_F16 for the one-term form of every variant (ISL_PREC_FP16: the same plan, tiles and K
-// order on hi-only operands), X3V_F16 | X3V_A16 for its fp16-storage form (ISL_ACT_FP16), 0 for the
-// three-term kernels
-template <int KS, int FV>
-static hipError_t launch_ks(const ConvLaunch& c, hipStream_t s) {
-  if constexpr (KS == 3) {
-    if (x3_big_tiles(c) && x3_union(c)) {
-#ifdef ISLPOSE_DEV
-      if (x3_union_mode() == 4 && c.dbg) {   // development build only (tools/convbench)
-        switch (c.bco) {
-          case 128: return launch_t<KS, 2, 8, 2, 2, 512 | 16384 | FV, 4>(c, s);
-          case 96: return launch_t<KS, 1, 16, 3, 1, 512 | 16384 | FV, 4>(c, s);
-        }
-      }
-#endif
-#ifdef ISLPOSE_DEV
-      const bool m16 = FV == 0 && c.bco == 128 && x3_m16(c);   // (three-term only)
-      if constexpr (FV == 0) if (m16) {
-        if (c.vin) return launch_t<KS, 2, 8, 2, 2, 512 | 32768 | 131072 | FV, 4>(c, s);
-        return launch_t<KS, 2, 8, 2, 2, 512 | 131072 | FV, 4>(c, s);
-      }
-#endif
-      if (c.vin) {
-        if (c.bco == 128) return launch_t<KS, 2, 8, 2, 2, 512 | 32768 | FV, 4>(c, s);
-        set_error("conv_x3: pooled-input staging without a variant (x3_vin_ok)");
-        return hipErrorInvalidValue;
-      }
-      switch (c.bco) {
-        case 128: return launch_t<KS, 2, 8, 2, 2, 512 | FV, 4>(c, s);
-        case 96: return launch_t<KS, 1, 16, 3, 1, 512 | FV, 4>(c, s);
-        case 64: return launch_t<KS, 2, 8, 1, 2, 512 | FV, 4>(c, s);
-        case 32: return launch_t<KS, 1, 16, 1, 1, 512 | FV, 4>(c, s);
-      }
-    }
-  }
-  if constexpr (KS == 1) {
-    if (c.bco == 256 && x3_big_tiles(c)) return launch_t<KS, 4, 4, 2, 2, 4096 | FV, 1>(c, s);
-  }
-  if constexpr (KS <= 3) {
-    if (x3_big_tiles(c)) {
-      if constexpr (KS == 3) {
-        if (c.vin) {
-          if (c.bco == 128) return launch_t<KS, 2, 8, 2, 2, 32768 | FV, 4>(c, s);
-          if (x3_half64(c)) return launch_t<KS, 1, 8, 2, 1, 32768 | FV, 2>(c, s);
-        }
-      }
-      if (c.vin) {
-        set_error("conv_x3: pooled-input staging without a variant (x3_vin_ok)");
-        return hipErrorInvalidValue;
-      }
-      if (x3_half64(c)) return launch_t<KS, 1, 8, 2, 1, FV, 2>(c, s);   // 8 waves of 64co x 32px, 256 px
-      switch (c.bco) {
-        case 128: return launch_t<KS, 2, 8, 2, 2, FV, 4>(c, s);   // 16 waves, 64co x 64px each
-        case 96: return launch_t<KS, 1, 16, 3, 1, FV, 4>(c, s);   // 16 waves, 96co x 32px
-        case 64: return launch_t<KS, 2, 8, 1, 2, FV, 4>(c, s);    // 16 waves, 32co x 64px
-        case 32: return launch_t<KS, 1, 16, 1, 1, FV, 4>(c, s);   // 16 waves, 32co x 32px
-      }
-    }
-  }
-  if constexpr (KS == 7) {
-    // 128-channel 7x7 tiles without K ranges: 8 waves of 64co x 64px on 256 pixels, or
-    // of 64co x 32px on 128 pixels (one block per CU either way: the 56 KiB weight
-    // slabs; 8 waves measured 2-6 % over 4 waves of 64co x 64px / x 128px)
-    if (c.ksplit <= 1 && c.bco == 128) {
-      if (x3_small7(c)) {   // 64co x 64px blocks (=2: the steps' operands two steps ahead)
-        if (x3_small7_96(c)) return launch_t<KS, 2, 3, 1, 1, 256 | 128 | FV, 1>(c, s);
-        if (x3_small7_deep(c)) return launch_t<KS, 2, 2, 1, 1, 256 | 128 | FV, 1>(c, s);
-        return launch_t<KS, 2, 2, 1, 1, 256 | FV, 4>(c, s);
-      }
-      if (x3_wide7_384(c)) return launch_t<KS, 2, 6, 2, 2, 65536 | FV, 1>(c, s);   // 12 waves, 384 px
-      if (x3_wide7(c)) return launch_t<KS, 2, 4, 2, 2, FV, 1>(c, s);
-      return launch_t<KS, 2, 4, 2, 1, FV, 1>(c, s);
-    }
-  }
-  const bool ranged = c.ksplit > 1 && !c.ws;      // launch_conv_x3: in-block ranges
-  const bool split = c.ksplit > 1 && c.ws;        // across blocks
-  // 128- / 96-channel tiles of the 128-pixel family: 8 waves of 64co x 32px / 12 waves of
-  // 32co x 32px rather than 4 waves of 64co x 64px / 96co x 32px.  These grids are small
-  // (Mode R's 23x41 stages: one block per CU at batch 32), and two or three waves per
-  // SIMD hide the staging: -8 to -22 % on the 23x41 3x3 stage layers, -12 to -31 % on
-  // their 1x1 layers, -5 to -14 % on the hand's 23^2 7x7 layers, -20 % on its 23^2 c512
-  // layers (tools/archive/gpu_s8.sh, gpu_s8b.sh).  ISLPOSE_X3_S8=0: the 4-wave layouts (A/B).
-  static const int more = getenv("ISLPOSE_X3_S8") ? atoi(getenv("ISLPOSE_X3_S8")) : 1;
-  if (more) {
-    {
-#ifdef ISLPOSE_DEV
-      if constexpr (KS <= 3) {
-        if (c.fold) {   // consumers of folded split-K partials (x3_fold_ok)
-          switch (c.bco) {
-            case 128:
-              if (split) return launch_t<KS, 2, 4, 2, 1, 2048 | 8192 | FV, 2>(c, s);
-              if (ranged) return launch_t<KS, 2, 4, 2, 1, 1024 | 8192 | FV, 2>(c, s);
-              return launch_t<KS, 2, 4, 2, 1, 8192 | FV, 2>(c, s);
-            case 96:
-              if (split) return launch_t<KS, 3, 4, 1, 1, 2048 | 8192 | FV, 2>(c, s);
-              if (ranged) return launch_t<KS, 3, 4, 1, 1, 1024 | 8192 | FV, 2>(c, s);
-              return launch_t<KS, 3, 4, 1, 1, 8192 | FV, 2>(c, s);
-          }
-          set_error("conv_x3: fold without a variant (x3_fold_ok)");
-          return hipErrorInvalidValue;
-        }
-      }
-#else
-      if (c.fold) {
-        set_error("conv_x3: the split-K fold is a development-build variant");
-        return hipErrorInvalidValue;
-      }
-#endif
-      if constexpr (KS <= 3) {
-        if (x3_g2(c)) return launch_t<KS, 2, 4, 2, 1, 1024 | 32 | FV, 1>(c, s);   // two K groups of 8 waves
-      }
-      if constexpr (KS <= 3) {
-        if (!split && !ranged && x3_halfsmall(c)) return launch_t<KS, 1, 4, 2, 1, 256 | FV, 4>(c, s);
-      }
-      if constexpr (KS <= 3) {
-        if (x3_deep(c)) {   // prefetch two K steps ahead
-          switch (c.bco) {
-            case 128:
-              if (split) return launch_t<KS, 2, 4, 2, 1, 2048 | 128 | FV, 1>(c, s);
-              if (ranged) return launch_t<KS, 2, 4, 2, 1, 1024 | 128 | FV, 1>(c, s);
-              return launch_t<KS, 2, 4, 2, 1, 128 | FV, 1>(c, s);
-            case 96:
-              if (split) return launch_t<KS, 3, 4, 1, 1, 2048 | 128 | FV, 1>(c, s);
-              if (ranged) return launch_t<KS, 3, 4, 1, 1, 1024 | 128 | FV, 1>(c, s);
-              return launch_t<KS, 3, 4, 1, 1, 128 | FV, 1>(c, s);
-          }
-        }
-      }
-#ifdef ISLPOSE_DEV
-      if constexpr (KS <= 3) {
-        if (x3_pps2(c)) {   // two chunk pairs per K step: twice the MFMAs between barriers
-          switch (c.bco) {
-            case 128:
-              if (split) return launch_t<KS, 2, 4, 2, 1, 2048 | 4096 | FV, 2>(c, s);
-              if (ranged) return launch_t<KS, 2, 4, 2, 1, 1024 | 4096 | FV, 2>(c, s);
-              return launch_t<KS, 2, 4, 2, 1, 4096 | FV, 2>(c, s);
-            case 96:
-              if (split) return launch_t<KS, 3, 4, 1, 1, 2048 | 4096 | FV, 2>(c, s);
-              if (ranged) return launch_t<KS, 3, 4, 1, 1, 1024 | 4096 | FV, 2>(c, s);
-              return launch_t<KS, 3, 4, 1, 1, 4096 | FV, 2>(c, s);
-          }
-        }
-      }
-#endif
-      if (c.bco == 128 && x3_halfco(c)) {   // two blocks of 4 waves (64co x 32px) per 128-channel tile
-        if constexpr (KS == 7) {
-          if (split && x3_small7_deep(c)) return launch_t<KS, 2, 2, 1, 1, 2048 | 256 | 128 | FV, 1>(c, s);
-        }
-        if (split && x3_px64_mode() >= 2) return launch_t<KS, 2, 2, 1, 1, 2048 | 256 | FV, 4>(c, s);
-        if (split) return launch_t<KS, 1, 4, 2, 1, 2048 | 256 | FV, 4>(c, s);
-#ifdef ISLPOSE_DEV
-        if (ranged) return launch_t<KS, 1, 4, 2, 1, 1024 | 256 | FV, 4>(c, s);
-#endif
-        if (!ranged) return launch_t<KS, 1, 4, 2, 1, 256 | FV, 4>(c, s);
-      }
-      switch (c.bco) {
-        case 128:   // 8 waves of 64co x 32px
-          if (split) return launch_t<KS, 2, 4, 2, 1, 2048 | FV, 2>(c, s);
-          if (ranged) return launch_t<KS, 2, 4, 2, 1, 1024 | FV, 2>(c, s);
-          return launch_t<KS, 2, 4, 2, 1, FV, 2>(c, s);
-        case 96:    // 12 waves of 32co x 32px (6 on 64-pixel tiles: x3_px64)
-          if (split && x3_px64(c)) return launch_t<KS, 3, 2, 1, 1, 2048 | FV, 4>(c, s);
-          if (split) return launch_t<KS, 3, 4, 1, 1, 2048 | FV, 2>(c, s);
-          if (ranged) return launch_t<KS, 3, 4, 1, 1, 1024 | FV, 2>(c, s);
-          return launch_t<KS, 3, 4, 1, 1, FV, 2>(c, s);
-      }
-    }
-  }
-  switch (c.bco) {
-#define X3_CASE(BC, WMS, WNS, WMM, WNN)                                           \
-  case BC:                                                                        \
-    if (split) return launch_t<KS, WMS, WNS, WMM, WNN, 2048 | FV, 2>(c, s);            \
-    if (ranged) return launch_t<KS, WMS, WNS, WMM, WNN, 1024 | FV, 2>(c, s);           \
-    return launch_t<KS, WMS, WNS, WMM, WNN, FV, 2>(c, s);
-    X3_CASE(128, 2, 2, 2, 2)
-    X3_CASE(96, 1, 4, 3, 1)
-    X3_CASE(64, 1, 4, 2, 1)
-    X3_CASE(32, 1, 4, 1, 1)
-#undef X3_CASE
-  }
-  set_error("conv_x3: unsupported tile");
-  return hipErrorInvalidValue;
-}
-
-bool x3_fits(const ConvLaunch& c) { return c.in_pad >= c.ks / 2; }
-
-// Launches with a pooled-input variant (VAR 32768): 3x3 layers on the 512-pixel family
-// with 128-channel tiles (row union or generic) or the 256-pixel 64-channel blocks -- the
-// layers after the body's and hand's pools at batch sizes that fill the chip.  Others
-// take vpool2_kernel + the plain variant.
-bool x3_vin_ok(const ConvLaunch& c) {
-  return x3_fits(c) && c.ks == 3 && c.in_coff == 0 && x3_ranges(c).S == 1 && x3_big_tiles(c) &&
-         (c.bco == 128 || x3_half64(c)) && (long long)(c.H + 2 * c.in_pad) * (c.W + 2 * c.in_pad) < (1 << 20);
-}
-
-bool x3_hpool_ok(const ConvLaunch& c) {
-  return x3_fits(c) && !(c.W & 1) && !(x3_ranges(c).S > 1 && x3_ranges(c).across_blocks);
-}
-
-double conv_x3_mfma_flops(const ConvLaunch& c) {
-  const int BPX = x3_big_tiles(c) ? x3_big_bpx(c) : x3_wide7_384(c) ? 384 : x3_wide7(c) ? 256 : 128;
-  const double co = (double)((c.cout + c.bco - 1) / c.bco) * c.bco;
-  const double px = std::ceil((double)c.H * c.W / tile_pixels(c, BPX, x3_segmax(BPX))) * BPX;
-  return x3_products(c) * 2.0 * co * (((c.cin_chunks + 1) / 2) * 16.0) * c.ks * c.ks * px * c.n;
-}
-
-int x3_split_ranges(const ConvLaunch& c, bool* across_blocks) {
-  const X3Ranges r = x3_ranges(c);
-  if (across_blocks) *across_blocks = r.across_blocks;
-  return r.S;
-}
-
-bool x3_fold_ok(const ConvLaunch& c) {
-  static const int more = getenv("ISLPOSE_X3_S8") ? atoi(getenv("ISLPOSE_X3_S8")) : 1;
-  return more && x3_fits(c) && c.ks <= 3 && !c.vin && !c.hpool && (c.bco == 128 || c.bco == 96) &&
-         !x3_big_tiles(c) && (long long)(c.H + 2 * c.in_pad) * (c.W + 2 * c.in_pad) < (1 << 20);
-}
-
-size_t x3_splitk_ws_floats(const ConvLaunch& c) {
-  const X3Ranges r = x3_ranges(c);
-  return r.across_blocks ? (size_t)r.S * c.n * ((c.cout + 7) / 8) * 8 * c.H * c.W : 0;
-}
-
-bool x3_fused67_fits(int cout6, int cout7) {
-  return (cout6 == 128 || cout6 == 256 || cout6 == 512) && cout7 > 0 && cout7 <= 64;
-}
-
-// The fused 1x1 pair, one tile of every Mconv6 channel: 16 waves of 64co x 64px, 8 x 2
-// (512 channels, 128 pixels), 4 x 4 (256, 256) or 2 x 8 (128, 512).  No K ranges: the pair
-// always runs fused, at every batch size, so a frame's bits do not depend on its batch.
-static hipError_t launch_x3_fused67(ConvLaunch c, hipStream_t s) {
-  if (c.ks != 1 || !x3_fused67_fits(c.cout, c.cout7)) {
-    set_error("conv_x3: fused 1x1 pair outside its shapes");
-    return hipErrorInvalidValue;
-  }
-  c.ksplit = 1;
-  c.ws = nullptr;
-  c.bco = c.cout;
-  // (two chunk pairs per K step with one input buffer, VAR 4096 | 65536, measured level with
-  // this loop in Mode N and Mode R, profiles/r04/r4c/ops_*_pps1.txt: not built)
-  // ISL_PREC_FP16: the one-term form (VAR 16 | 2: the one-term generic loop, one rounding of
-  // Mconv6's value, hi-only pack_x3_f7), with fp16 buffers on both sides under ISL_ACT_FP16 (| 1)
-  if (c.act16) {
-    switch (c.cout) {
-      case 512: return launch_t<1, 8, 2, 2, 2, 16 | X3V_F16 | X3V_A16, 4>(c, s);
-      case 256: return launch_t<1, 4, 4, 2, 2, 16 | X3V_F16 | X3V_A16, 4>(c, s);
-      case 128: return launch_t<1, 2, 8, 2, 2, 16 | X3V_F16 | X3V_A16, 4>(c, s);
-    }
-  } else if (c.f16) {
-    switch (c.cout) {
-      case 512: return launch_t<1, 8, 2, 2, 2, 16 | X3V_F16, 4>(c, s);
-      case 256: return launch_t<1, 4, 4, 2, 2, 16 | X3V_F16, 4>(c, s);
-      case 128: return launch_t<1, 2, 8, 2, 2, 16 | X3V_F16, 4>(c, s);
-    }
-  } else
-  switch (c.cout) {
-    case 512: return launch_t<1, 8, 2, 2, 2, 16, 4>(c, s);
-    case 256: return launch_t<1, 4, 4, 2, 2, 16, 4>(c, s);
-    case 128: return launch_t<1, 2, 8, 2, 2, 16, 4>(c, s);
-  }
-  set_error("conv_x3: fused 1x1 pair outside its shapes");
-  return hipErrorInvalidValue;
-}
-
-// The pair runs fused where its grid has at least half a block per CU; smaller grids (batch-1
-// Mode R: 8 pixel tiles) take the two launches (Mconv6 then Mconv7 with its K ranges split
-// across blocks), whose bits are the fused kernel's (the runtime's permuted Mconv6 output order,
-// pack_x3 with the Mconv7 channel map; x3_canonical_order over the waves).
-bool x3_fused67_grid(const ConvLaunch& c) {
-  const int bpx = c.cout == 512 ? 128 : c.cout == 256 ? 256 : 512;
-  const long long blocks = (long long)c.n * ((c.H * c.W + tile_pixels(c, bpx, x3_segmax(bpx)) - 1) /
-                                             tile_pixels(c, bpx, x3_segmax(bpx)));
-  return 2 * blocks >= device_cus();
-}
-
-double conv_x3_fused67_mfma_flops(const ConvLaunch& c) {
-  const int bpx = c.cout == 512 ? 128 : c.cout == 256 ? 256 : 512;
-  const double px = std::ceil((double)c.H * c.W / tile_pixels(c, bpx, x3_segmax(bpx))) * bpx * c.n;
-  const double k6 = ((c.cin_chunks + 1) / 2) * 16.0;
-  return x3_products(c) * 2.0 * px * ((double)c.cout * k6 + 32.0 * ((c.cout7 + 31) / 32) * c.cout);
-}
-
-
-// conv_x3_wr for the launches whose K ranges would run across blocks (x3_ranges), by default
-// those with at most 4 ranges; ISLPOSE_X3_WR=0: the split-K launches + x3_splitk_reduce (A/B),
-// =2: also the small grids without K ranges (one wave per block summing the whole K; A/B), =3:
-// every range count; ISLPOSE_X3_WR_WN=2: 64-pixel tiles (two 32-pixel accumulator tiles per wave
-// sharing the weight fragments).  Read per launch.
-static int x3_wr_mode() {
-  const char* e = getenv("ISLPOSE_X3_WR");
-  return e ? atoi(e) : 1;
-}
-
+// The argument fill and the checks of one conv_x3_wr instance: ch.S waves per block, one K range each
 template <int KS, int WN, int DEPTH>
-static hipError_t launch_wr_t(const ConvLaunch& c, int S, hipStream_t s) {
+static hipError_t launch_wr_t(const ConvLaunch& c, const X3Choice& ch, int, const X3Switches&, hipStream_t s) {
+  const int S = ch.S;
   constexpr int P = KS / 2;
   if (c.in_pad < P) { set_error("conv_x3_wr: input ring narrower than kernel radius"); return hipErrorInvalidValue; }
   if ((c.in_cs | c.in_coff | c.out_cs | c.out_coff) & 7) { set_error("conv_x3_wr: slice not on a chunk"); return hipErrorInvalidValue; }
@@ -2803,42 +2108,46 @@ static hipError_t launch_wr_t(const ConvLaunch& c, int S, hipStream_t s) {
   const long long nb = (long long)c.n * a.px_tiles * a.co_tiles;
   if (nb <= 0 || nb > 0x7fffffff) { set_error("conv_x3_wr: bad grid"); return hipErrorInvalidValue; }
   a.nblocks = (int)nb;
-  t_last_variant = x3_variant_code(8 | (S > 1 ? 1024 : 0) | (c.f16 ? X3V_F16 : 0), KS, 32 * WN, 32);
   if (c.f16) hipLaunchKernelGGL((conv_x3_wr<KS, WN, DEPTH, true>), dim3(a.nblocks), dim3(64 * S), 0, s, a);
   else hipLaunchKernelGGL((conv_x3_wr<KS, WN, DEPTH, false>), dim3(a.nblocks), dim3(64 * S), 0, s, a);
   return hipGetLastError();
 }
 
-static hipError_t launch_x3_wr(const ConvLaunch& c, int S, hipStream_t s) {
-  const char* e = getenv("ISLPOSE_X3_WR_WN");
-  const bool wn2 = e && e[0] == '2';
-  switch (c.ks) {
-    case 1: return wn2 ? launch_wr_t<1, 2, 8>(c, S, s) : launch_wr_t<1, 1, 12>(c, S, s);
-    case 3: return wn2 ? launch_wr_t<3, 2, 8>(c, S, s) : launch_wr_t<3, 1, 12>(c, S, s);
-    case 7: return wn2 ? launch_wr_t<7, 2, 8>(c, S, s) : launch_wr_t<7, 1, 12>(c, S, s);
+// The launchers of the instances (x3_instances.h): a choice's tuple, packed, to its launch_t /
+// launch_wr_t.  This table is what instantiates the kernels.
+typedef hipError_t (*X3LaunchFn)(const ConvLaunch&, const X3Choice&, int, const X3Switches&, hipStream_t);
+struct X3Instance {
+  unsigned long long key;
+  X3LaunchFn fn;
+};
+constexpr unsigned long long x3_key(bool wr, int ks, int a, int b, int c, int d, int var, int occ) {
+  return (unsigned long long)wr | (unsigned long long)ks << 1 | (unsigned long long)a << 4 | (unsigned long long)b << 8 |
+         (unsigned long long)c << 13 | (unsigned long long)d << 15 | (unsigned long long)occ << 17 |
+         (unsigned long long)var << 20;
+}
+template <int KS, int A, int B, int C, int D, int VAR, int OCC, bool BUILT>
+constexpr X3LaunchFn x3_form() {
+  if constexpr (BUILT) return &launch_t<KS, A, B, C, D, VAR, OCC>;
+  else return nullptr;
+}
+static const X3Instance kX3Instances[] = {
+#define X3_F16(KS, A, B, C, D, VAR, OCC, FORMS)                                                                     \
+  {x3_key(false, KS, A, B, C, D, VAR, OCC), x3_form<KS, A, B, C, D, VAR, OCC, ((FORMS) & 1) != 0>()},                \
+  {x3_key(false, KS, A, B, C, D, (VAR) | X3V_F16, OCC), x3_form<KS, A, B, C, D, (VAR) | X3V_F16, OCC, ((FORMS) & 2) != 0>()}, \
+  {x3_key(false, KS, A, B, C, D, (VAR) | X3V_F16 | X3V_A16, OCC),                                                   \
+   x3_form<KS, A, B, C, D, (VAR) | X3V_F16 | X3V_A16, OCC, ((FORMS) & 4) != 0>()},
+#define X3_WR(KS, WN, DEPTH, FORMS) {x3_key(true, KS, 0, 0, 0, WN, DEPTH, 0), &launch_wr_t<KS, WN, DEPTH>},
+#include "x3_instances.h"
+#undef X3_F16
+#undef X3_WR
+};
+
+hipError_t launch_conv_x3(const ConvLaunch& c0, const X3Choice& ch, const X3Switches& sw, hipStream_t s) {
+  if (ch.family == X3Choice::NONE || ch.family == X3Choice::RGB) {
+    set_error(ch.error ? ch.error : "conv_x3: not a conv_x3 choice");
+    return hipErrorInvalidValue;
   }
-  set_error("conv_x3_wr: unsupported kernel size");
-  return hipErrorInvalidValue;
-}
-
-bool x3_act16_ok(const ConvLaunch& c0) {
-  if (!c0.f16 || c0.fold || c0.fold_out || !x3_fits(c0)) return false;
-  // the fused 1x1 pair (VAR 16 | 2 | 1): one tile of every Mconv6 channel, no K ranges
-  if (c0.cout7 > 0) return c0.ks == 1 && x3_fused67_fits(c0.cout, c0.cout7) && !c0.hpool && !c0.vin;
-  if (c0.ks != 1 && c0.ks != 3 && c0.ks != 7) return false;
-  ConvLaunch c = c0;
-  const X3Ranges r = x3_ranges(c);
-  c.ksplit = r.S;
-  c.ws = nullptr;
-  // K ranges across blocks (the wave-range kernel or split-K + x3_splitk_reduce) and the A/B
-  // mode that runs the other small grids on the wave-range kernel
-  if (r.across_blocks || x3_wr_mode() == 2) return false;
-  if (c.ks == 7 && c.ksplit <= 1 && c.bco == 128 && x3_small7(c) && x3_small7_96(c)) return false;
-  return true;
-}
-
-hipError_t launch_conv_x3(const ConvLaunch& c0, hipStream_t s) {
-  if (c0.act16 && !x3_act16_ok(c0)) {
+  if (c0.act16 && !ch.act16) {
     set_error("conv_x3: launch without an fp16-storage form (the runtime plans such runs on fp32 buffers)");
     return hipErrorInvalidValue;
   }
@@ -2846,35 +2155,42 @@ hipError_t launch_conv_x3(const ConvLaunch& c0, hipStream_t s) {
     set_error("conv_x3: fp32 output copy outside fp16 storage");
     return hipErrorInvalidValue;
   }
-  if (c0.cout7 > 0) return launch_x3_fused67(c0, s);
   ConvLaunch c = c0;
-  const X3Ranges r = x3_ranges(c);
-  c.ksplit = r.S;
-  // wave ranges where a 1x1 / 3x3 layer has at most 4 K ranges: with 8 a block's 8 waves load 2x
-  // the operand bytes per CU of the split-K blocks (no sharing between ranges), and in the net the
-  // c384 / c288 stage layers ran 20-35 % slower on it (profiles/r05/r5c/ops_*.txt); a 7x7 range
-  // is 98 taps long for one wave (the hand's 184-pixel scale: C3 109.4 -> 107.5 frames/s on it,
-  // profiles/r05/r5n/)
-  if (r.across_blocks && !c.fold_out && (x3_wr_mode() >= 3 || (x3_wr_mode() >= 1 && r.S <= 4 && c.ks <= 3)))
-    return launch_x3_wr(c, r.S, s);
-  if (x3_wr_mode() == 2 && r.S == 1 && c.ks <= 3 && !c.hpool && !c.vin && !c.fold && !x3_big_tiles(c) &&
-      x3_7x7_bpx(c) == 128)
-    return launch_x3_wr(c, 1, s);
-  if (r.across_blocks) {
-    if (!c.ws || (size_t)r.S * c.n * ((c.cout + 7) / 8) * 8 * c.H * c.W > c.ws_floats) {
+  c.ksplit = ch.S;
+  const bool wr = ch.family == X3Choice::WR;
+  if (ch.family == X3Choice::FUSED67) {
+    c.ws = nullptr;
+    c.bco = c.cout;
+  } else if (ch.across_blocks && !wr) {
+    if (!c.ws || ch.ws_floats > c.ws_floats) {
       set_error("conv_x3: split-K workspace too small");
       return hipErrorInvalidValue;
     }
-  } else {
+  } else if (!wr) {
     c.ws = nullptr;        // in-block ranges (or none)
   }
-  switch (c.ks) {
-    case 1: return c.act16 ? launch_ks<1, X3V_F16 | X3V_A16>(c, s) : c.f16 ? launch_ks<1, X3V_F16>(c, s) : launch_ks<1, 0>(c, s);
-    case 3: return c.act16 ? launch_ks<3, X3V_F16 | X3V_A16>(c, s) : c.f16 ? launch_ks<3, X3V_F16>(c, s) : launch_ks<3, 0>(c, s);
-    case 7: return c.act16 ? launch_ks<7, X3V_F16 | X3V_A16>(c, s) : c.f16 ? launch_ks<7, X3V_F16>(c, s) : launch_ks<7, 0>(c, s);
-  }
-  set_error("conv_x3: unsupported kernel size");
+  const unsigned long long key = wr ? x3_key(true, ch.ks, 0, 0, 0, ch.wn, ch.depth, 0)
+                                    : x3_key(false, ch.ks, ch.waves_m, ch.waves_n, ch.wm, ch.wn, ch.var, ch.occ);
+  // (the forms that are not built have no launcher; sorted once, then a binary search per launch)
+  static const std::vector<X3Instance> table = [] {
+    std::vector<X3Instance> t;
+    for (const X3Instance& i : kX3Instances)
+      if (i.fn) t.push_back(i);
+    std::sort(t.begin(), t.end(), [](const X3Instance& a, const X3Instance& b) { return a.key < b.key; });
+    return t;
+  }();
+  const auto it = std::lower_bound(table.begin(), table.end(), key, [](const X3Instance& i, unsigned long long k) { return i.key < k; });
+  if (it != table.end() && it->key == key) return it->fn(c, ch, device_cus(), sw, s);
+  set_error("conv_x3: no instance " + std::string(wr ? "conv_x3_wr<" : "conv_x3_f16<") + std::to_string(ch.ks) + ", " +
+            (wr ? std::to_string(ch.wn) + ", " + std::to_string(ch.depth)
+                : std::to_string(ch.waves_m) + ", " + std::to_string(ch.waves_n) + ", " + std::to_string(ch.wm) + ", " +
+                      std::to_string(ch.wn) + ", " + std::to_string(ch.var) + ", " + std::to_string(ch.occ)) +
+            "> (x3_instances.h)");
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_conv_x3(const ConvLaunch& c, const X3Switches& sw, hipStream_t s) {
+  return launch_conv_x3(c, x3_choose(c, device_cus(), sw), sw, s);
 }
 
 }  // namespace isl

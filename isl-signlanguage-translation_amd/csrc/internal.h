@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <string>
 
+#include "x3_select.h"
+
 namespace isl {
 
 // Activation buffer: float32 in 8-channel chunks ("NC8HW8"), with a zero ring of
@@ -30,91 +32,8 @@ struct Act {
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_PRELU = 2 };
 
-// One input chunk of a split-fp16 conv whose producer left split-K partial sums instead
-// of its output (ConvLaunch::fold, conv_x3 VAR 8192): the consumer's staging sums them in
-// range order and applies the producer's epilogue, exactly as x3_splitk_reduce would have
-// (the reduce launch is skipped).  ws == nullptr: the chunk is read from the buffer.
-struct X3Fold {
-  const float* ws;          // partials of this chunk: + n * fstride + m * 8 + k * sstride (range k)
-  long long fstride, sstride;
-  const float* bias;        // 8 values of the chunk
-  const float* slope;       // 8 PReLU slopes (act == ACT_PRELU)
-  float scale;              // the producer's 2^-s
-  int S, act, pad_;
-};
-
-// One convolution launch.
-struct ConvLaunch {
-  const float* in;  int in_pad, in_cs, in_coff;
-  float* out;       int out_pad, out_cs, out_coff;
-  const float* wpk;            // packed weights  [co_tile][chunk][ky][kx][plane][BCO][4]
-  const float* bias;           // [co_tiles*BCO]
-  const float* slope;          // [co_tiles*BCO] or null
-  int n, H, W;
-  int ks;                      // 1, 3, 7
-  int cin_chunks;              // physical input channels / 8
-  int cout;                    // real output channels
-  int bco;                     // output channels per block tile (32, 64, 96, 128)
-  int act;
-  // split-fp16 path (conv_x3.hip)
-  const void* wx3 = nullptr;   // pre-split weights [co_tile][pair][ky][kx][hi|lo][h][BCO][8] fp16
-  float wscale_inv = 1.f;      // 2^-s, the inverse of the per-layer weight scale
-  int* range_flag = nullptr;   // raised when an output leaves the fp16 split range
-  // ISL_PREC_FP16: one fp16 product per MAC.  wx3 then holds the hi halves alone -- the same
-  // layouts without their [hi|lo] dimension (runtime.cpp pack_hi_only) -- and the kernels
-  // round the activations to fp16 once at staging; launch_conv_x3 (the fused pair included: wx3f7
-  // is then the hi-only pack_x3_f7), launch_conv_x3_rgb and launch_conv_x3_c12 (both launches set it)
-  int f16 = 0;
-  // ISL_ACT_FP16 (with f16 only): `in` and `out` are fp16 buffers (Act::esize 2; the strides in
-  // elements are the same), the staging copies the stored roundings and the epilogue stores
-  // RNE(v) after its range check on the fp32 value.  launch_conv_x3_rgb reads its fp32 net input
-  // as ever and writes fp16.  out32 (a layer that writes a net output): the unrounded fp32
-  // values also go to channels [0, cout) of this fp32 buffer of out32_cs channels, ring out32_pad
-  int act16 = 0;
-  float* out32 = nullptr;
-  int out32_pad = 0, out32_cs = 0;
-  // split-K workspace (conv_x3 on grids too small to fill the GPU); null = no split
-  float* ws = nullptr;
-  size_t ws_floats = 0;
-  int ksplit = 1;              // set by launch_conv_x3
-  int allow_split = 0;         // the net's split-K switch (isl_net_set_split_k)
-  unsigned long long* dbg = nullptr;   // development stamps (tools/convbench), never set by the runtime
-  // Half of a following 2x2 max-pool (conv_x3 only, even W): the epilogue writes the
-  // max of each horizontal pixel pair into `out` as an unpadded [n][chunk][H][W/2][8]
-  // buffer (out_pad 0); launch_vpool2 then takes the max of row pairs.
-  int hpool = 0;
-  // The other half (conv_x3 only): `in` is such a pair-max buffer [n][chunk][2H][W][8] of
-  // the pool whose H x W output this conv reads; its staging takes the max of each row
-  // pair on the fly (the ring, in_pad wide, reads as zeros), so the pool kernel and its
-  // output buffer are skipped.  in_pad / in_cs / in_coff describe the pooled buffer.
-  int vin = 0;
-  // Split-K fold (conv_x3 only).  fold: device table [cin_chunks] of X3Fold for this conv's
-  // input chunks (a consumer); fold_out: this conv's across-block partial sums are consumed
-  // by folding consumers, so its x3_splitk_reduce launch is skipped (a producer).
-  const X3Fold* fold = nullptr;
-  int fold_out = 0;
-
-  // The fused 1x1 pair (conv_x3 VAR 16; Mconv6 -> Mconv7 of a stage, model.py:108-109):
-  // cout7 > 0 makes this launch the pair.  The fields above describe Mconv6 (wx3 packed for a
-  // tile of all its cout channels) with `out` / out_* describing Mconv7's output; these
-  // describe Mconv7 (wx3f7 = pack_x3_f7, K in the order of Mconv6's accumulator registers).
-  const void* wx3f7 = nullptr;
-  const float* bias7 = nullptr;
-  const float* slope7 = nullptr;
-  float wscale7_inv = 1.f;
-  int cout7 = 0, act7 = 0;
-};
-
-// Pixels per tile of the flattened-raster conv kernels: BPX, or fewer when the
-// image is so narrow that a BPX-pixel tile's padded input row segment (which
-// crosses up to (W+BPX-2)/W image rows, each adding 2*in_pad ring pixels) would
-// overflow the kernel's LDS segment capacity `segcap`.
-inline int tile_pixels(const ConvLaunch& c, int bpx, int segcap) {
-  const int P = c.ks / 2;
-  for (int t = bpx; t > 1; --t)
-    if (t - 1 + 2 * c.in_pad * ((c.W + t - 2) / c.W) + 2 * P + 1 <= segcap) return t;
-  return 1;
-}
+// ConvLaunch (one convolution launch), X3Fold and tile_pixels live in x3_select.h: the host-only
+// launch selection of the split-fp16 kernels reads them without a HIP header.
 
 // Returns the block tile width (output channels) the conv kernels use for cout.
 int conv_bco_for(int cout);
@@ -124,66 +43,20 @@ hipError_t launch_conv(const ConvLaunch& c, hipStream_t s);
 // the transformed filters [co_tile][chunk][xi 16][plane 2][BCO][4].
 int wino_bco_for(int cout);
 hipError_t launch_wino(const ConvLaunch& c, hipStream_t s);
-// Split-fp16 (3 x fp16 MFMA = fp32-accurate) direct convolution: same tiles as
-// launch_conv; x3_fits() says whether the input segment of a pixel tile fits.
-// 1x1 layers with x3_wide1_layer() also carry filters packed for 256-channel tiles,
-// used for a launch when x3_wide1(c with bco 256) says its grid is big enough.
-bool x3_wide1_layer(int ks, int cout, int cin_phys);
-bool x3_wide1(const ConvLaunch& c);
-// whether launch_conv_x3 has a pooled-input (ConvLaunch::vin) variant for this launch
-bool x3_vin_ok(const ConvLaunch& c);
-// conv1_1 (3 input channels in one chunk, 3x3, <= 64 outputs): K packed as the 27
-// real (ky, kx, c) values; c.wx3 then holds the pack_x3_rgb filters [kk][hi|lo][h][64][8].
-bool x3_rgb_fits(const ConvLaunch& c);
+// Split-fp16 (3 x fp16 MFMA = fp32-accurate) direct convolution (conv_x3.hip).  What a launch
+// runs is x3_choose's decision (x3_select.h, with every predicate the runtime plans by); the
+// launch takes the plan's choice, or makes it from the switches (isl_debug_conv, tools/convbench).
+hipError_t launch_conv_x3(const ConvLaunch& c, const X3Choice& ch, const X3Switches& sw, hipStream_t s);
+hipError_t launch_conv_x3(const ConvLaunch& c, const X3Switches& sw, hipStream_t s);
 hipError_t launch_conv_x3_rgb(const ConvLaunch& c, hipStream_t s);
-double conv_x3_rgb_mfma_flops(const ConvLaunch& c);
+// compute units of the current device (cached; 256 where the query fails): x3_choose's `cus`
+int device_cus();
 // conv1_1 -> conv1_2 -> pair-max (conv_c12.hip): l1 = conv1_1 (rgb-packed wx3), l2 = conv1_2 with
 // its hpool output.  f16 on both: the one-term form from the hi-only packs of both layers; act16
 // on both: l2.out is an fp16 buffer (the net input stays fp32)
 bool x3_c12_fits(const ConvLaunch& l1, const ConvLaunch& l2);
 hipError_t launch_conv_x3_c12(const ConvLaunch& l1, const ConvLaunch& l2, hipStream_t s);
 double conv_x3_c12_mfma_flops(const ConvLaunch& l1);
-hipError_t launch_conv_x3(const ConvLaunch& c, hipStream_t s);
-bool x3_fits(const ConvLaunch& c);
-// whether launch_conv_x3 would run c (f16 set, the fields as at its launch) on a kernel with an
-// fp16-storage form (ConvLaunch::act16): every one-term conv_x3_f16 variant (the fused 1x1 pair
-// included) but split-K across blocks, the fold and the 96-pixel small 7x7 tiles; not the
-// wave-range kernel
-bool x3_act16_ok(const ConvLaunch& c);
-// whether launch_conv_x3 can run c with hpool (even W, not split across blocks)
-bool x3_hpool_ok(const ConvLaunch& c);
-double conv_x3_mfma_flops(const ConvLaunch& c);
-// Which conv_x3 variant a launch ran (isl_net_op_info): the template's VAR bits (1 fp16
-// activation storage, 512 row
-// union, 1024 in-block K ranges, 2048 split-K across blocks, 4096 two pairs per step,
-// 32768 pooled-input staging, 65536 one input buffer), X3V_RGB for conv_x3_rgb, the tile
-// (pixels / 32 at bits 20-24, output channels / 32 at bits 25-28) and the kernel radius
-// (ks / 2) at bits 29-30.
-constexpr int X3V_RGB = 1 << 18;
-constexpr int X3V_FOLD_OUT = 1 << 19;   // a split-K producer whose reduce was folded into its consumers
-constexpr int X3V_C12 = 4;              // conv1_1 -> conv1_2 -> pair-max in one launch (conv_c12.hip)
-constexpr int X3V_W2 = 64;              // split-fp16 Winograd F(2x2, 3x3) (wino_f16.hip)
-constexpr int X3V_F16 = 2;              // one-term fp16 products (ISL_PREC_FP16; a template VAR bit too)
-constexpr int X3V_A16 = 1;              // reads / writes fp16 activations (ISL_ACT_FP16; a template VAR bit, with X3V_F16)
-
-constexpr int x3_variant_code(int var, int ks, int bpx, int bco) {
-  return (var & 0xfffff) | ((bpx / 32) << 20) | ((bco / 32) << 25) | ((ks / 2) << 29);
-}
-int x3_last_variant();
-// whether launch_conv_x3 has a fused-pair variant for a 1x1 layer of cout6 outputs followed by
-// a 1x1 layer of cout7 outputs reading all of them (VAR 16)
-bool x3_fused67_fits(int cout6, int cout7);
-// whether a fusable pair's launch has the grid for the fused kernel (else two launches)
-bool x3_fused67_grid(const ConvLaunch& c);
-// MFMA FLOPs a fused-pair launch executes (both layers, tile padding included)
-double conv_x3_fused67_mfma_flops(const ConvLaunch& c);
-// floats of split-K workspace launch_conv_x3 would use for c (0 = no split)
-size_t x3_splitk_ws_floats(const ConvLaunch& c);
-// K ranges launch_conv_x3 would use for c: S, and whether they run across blocks (split-K
-// through the workspace) -- the producers a consumer can fold
-int x3_split_ranges(const ConvLaunch& c, bool* across_blocks);
-// whether launch_conv_x3 would run c on its generic loop (the loop that can fold)
-bool x3_fold_ok(const ConvLaunch& c);
 // Split-fp16 Winograd F(2x2,3x3) (wino_x3.hip): 3x3 layers with cout % 4 == 0;
 // c.wx3 then holds the split transformed filters [co_tile][pair][xi][hi|lo][h][64][8].
 hipError_t launch_wino_x3(const ConvLaunch& c, hipStream_t s);

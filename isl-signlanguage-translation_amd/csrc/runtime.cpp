@@ -518,25 +518,21 @@ static void plan_fuse67(isl_net* net) {
 }
 
 // ISLPOSE_X3_FUSE67: 0 the pairs as two plain launches (natural channel order; A/B), 2 always
-// fused, 3 always the permuted two launches (tests), default by grid (x3_fused67_grid); read
-// per run.  ISL_PREC_FP16 (h16): the one-term forms of both exist, but the fused K order of Mconv7
+// fused, 3 always the permuted two launches (tests), default by grid (x3_fused67_grid).  ISL_PREC_FP16 (h16): the one-term forms of both exist, but the fused K order of Mconv7
 // is the permuted one, not the natural order of the mode's plain launches (round-off apart), so
 // there an unset switch keeps the plain launches (0); 1 selects by grid as the fp32 default does
-static int fuse67_mode(bool h16) {
-  const char* e = getenv("ISLPOSE_X3_FUSE67");
-  return e && e[0] >= '0' && e[0] <= '3' ? e[0] - '0' : h16 ? 0 : 1;
-}
+static int fuse67_mode(const X3Switches& sw, bool h16) { return sw.fuse67 >= 0 ? sw.fuse67 : h16 ? 0 : 1; }
 
 // What the run does with the fusable pair (op k, op k + 1) under mode f67: 0 the plain launches,
 // 1 the fused launch, 2 the permuted two launches -- only where Mconv7 has K ranges (canonical:
 // its ranges are the fused kernel's wave shares, so both forms give the same bits); larger planes
 // always fuse.  `act`: the plan's geometry.
 static ConvLaunch basic_launch(const isl_net* net, const std::vector<Act>& act, const Op& op);
-static int fuse67_form(const isl_net* net, const std::vector<Act>& act, size_t k, int f67) {
+static int fuse67_form(const isl_net* net, const std::vector<Act>& act, size_t k, int f67, int cus, const X3Switches& sw) {
   const Op& op = net->ops[k];
   if (!f67 || !op.fuse67) return 0;
-  if ((f67 == 3 || (f67 == 1 && !x3_fused67_grid(basic_launch(net, act, op)))) &&
-      x3_split_ranges(basic_launch(net, act, net->ops[k + 1]), nullptr) > 1)
+  if ((f67 == 3 || (f67 == 1 && !x3_fused67_grid(basic_launch(net, act, op), cus))) &&
+      x3_split_ranges(basic_launch(net, act, net->ops[k + 1]), nullptr, cus, sw) > 1)
     return 2;
   return 1;
 }
@@ -807,55 +803,35 @@ static int default_act_storage() {
 // VALU ops per (tile, channel), twice the time of the 6144 MFMA FLOPs they feed
 // at 64 output channels per block, and a 128 KB single-buffered step leaves
 // no room for more channels.  Kept for A/B and as the record of that finding.
-static bool x3_wino_enabled() {
-  static const bool on = getenv("ISLPOSE_X3_WINO") && getenv("ISLPOSE_X3_WINO")[0] == '1';
-  return on;
-}
+static bool x3_wino_enabled(const X3Switches& sw) { return sw.x3_wino != 0; }
 #endif
 
 // 3x3 layers on chip-filling grids through the split-fp16 Winograd F(2x2, 3x3) kernel
 // (wino_f16.hip: 2.25x fewer MFMAs, fp32-accurate like conv_x3) where wino_f16_fits;
-// ISLPOSE_X3_W2=0: conv_x3 everywhere (A/B; read per launch)
+// ISLPOSE_X3_W2=0: conv_x3 everywhere (A/B)
 // Default: layers with >= 256 input channels (32 chunks) -- measured faster than conv_x3 there
 // (46x82 c384->128 1.06-1.16x, 92x164 c256->256 1.04-1.12x, 46x82 c512->512 1.05-1.17x in
 // tools/convbench, profiles/r06/w2c/), slower on c128->128 (K = 128: 0.85-0.9x).
 // ISLPOSE_X3_W2=0 never, =1 every eligible launch (A/B, tests), default 2 = the K rule.
-static int w2_mode() {
-  const char* e = getenv("ISLPOSE_X3_W2");
-  return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 2;
-}
-static bool w2_enabled(const ConvLaunch& c) {
-  const int m = w2_mode();
+static int w2_mode(const X3Switches& sw) { return sw.w2; }
+static bool w2_enabled(const X3Switches& sw, const ConvLaunch& c) {
+  const int m = w2_mode(sw);
   return m == 1 || (m == 2 && c.cin_chunks >= 32);
 }
 
-// ISLPOSE_RGB_CONV=0: conv1_1 on the generic split-fp16 kernel (A/B; read per launch)
-static bool rgb_kernel_enabled() {
-  const char* e = getenv("ISLPOSE_RGB_CONV");
-  return !(e && e[0] == '0');
-}
-
+// The plan-level switches (x3_switches(), read once per run by plan_steps, so a test can compare
+// both settings in one process):
+// ISLPOSE_RGB_CONV=0: conv1_1 on the generic split-fp16 kernel (A/B)
+static bool rgb_kernel_enabled(const X3Switches& sw) { return sw.rgb_conv != 0; }
 // conv1_1 -> conv1_2 -> the 2x2 pool in one launch (conv_c12.hip) writing the pooled map;
 // ISLPOSE_C12=0: the two convs as their own launches, =2: the fused launch writing the pool's
-// pair-max buffer, finished by the next conv's staging (round-5 form; A/B, read per run)
-static int c12_mode() {
-  const char* e = getenv("ISLPOSE_C12");
-  return e && (e[0] == '0' || e[0] == '2') ? e[0] - '0' : 1;
-}
-
-// ISLPOSE_FUSED_POOL=0: the plain conv + maxpool2 path (A/B; read per run, so a test
-// can compare both in one process)
-static bool fused_pool_enabled() {
-  const char* e = getenv("ISLPOSE_FUSED_POOL");
-  return !(e && e[0] == '0');
-}
-
+// pair-max buffer, finished by the next conv's staging (round-5 form; A/B)
+static int c12_mode(const X3Switches& sw) { return sw.c12; }
+// ISLPOSE_FUSED_POOL=0: the plain conv + maxpool2 path (A/B)
+static bool fused_pool_enabled(const X3Switches& sw) { return sw.fused_pool != 0; }
 // ISLPOSE_POOL_INPUT=0: a fused pool's row-pair max runs as vpool2_kernel into the pooled
-// buffer instead of inside the next conv's staging (ConvLaunch::vin; A/B, read per run)
-static bool pool_input_enabled() {
-  const char* e = getenv("ISLPOSE_POOL_INPUT");
-  return !(e && e[0] == '0');
-}
+// buffer instead of inside the next conv's staging (ConvLaunch::vin; A/B)
+static bool pool_input_enabled(const X3Switches& sw) { return sw.pool_input != 0; }
 
 // Pool op k may leave its output unwritten and hand its pair-max buffer to op k+1 (vin):
 // op k+1 is an x3 conv (not the 3-channel rgb kernel) reading the whole pooled buffer,
@@ -878,13 +854,11 @@ static bool pool_into_next_conv(const isl_net* net, const std::vector<Act>& act,
   return true;
 }
 
-// ISLPOSE_X3_FOLD=1: split-K producers leave their partials to folding consumers (A/B; read
-// per run).  Off by default: at batch 1 (Mode R) the consumers' staging re-reads S partials
+// ISLPOSE_X3_FOLD=1: split-K producers leave their partials to folding consumers (A/B).  Off by default: at batch 1 (Mode R) the consumers' staging re-reads S partials
 // per element and kernel row, and the frame ran 427 -> 315 frames/s (profiles/r03/fold_ab/)
 static bool fold_enabled() {
 #ifdef ISLPOSE_DEV
-  const char* e = getenv("ISLPOSE_X3_FOLD");
-  return e && e[0] == '1';
+  return x3_switches().fold != 0;
 #else
   return false;   // rejected: development build only
 #endif
@@ -913,11 +887,11 @@ static ConvLaunch basic_launch(const isl_net* net, const std::vector<Act>& act, 
 // the epilogue.  *l1 / *l2 are the launches (h16: the one-term form from the hi-only packs, a16:
 // its fp16 output) on the geometry `act`.
 static int c12_form(const isl_net* net, const std::vector<Act>& act, size_t k, bool fuse_pools, bool h16, bool a16,
-                    ConvLaunch* l1, ConvLaunch* l2) {
+                    int cus, const X3Switches& sw, ConvLaunch* l1, ConvLaunch* l2) {
   const Op& op = net->ops[k];
-  const int c12m = c12_mode();
+  const int c12m = c12_mode(sw);
   if (!(net->algo == ISL_ALGO_X3 && op.type == 0 && fuse_pools && c12m && k + 2 < net->ops.size() &&
-        rgb_layer(net->layers[op.layer]) && rgb_kernel_enabled()))
+        rgb_layer(net->layers[op.layer]) && rgb_kernel_enabled(sw)))
     return 0;
   const Op& o2 = net->ops[k + 1];
   const Op& pl = net->ops[k + 2];
@@ -939,7 +913,7 @@ static int c12_form(const isl_net* net, const std::vector<Act>& act, size_t k, b
   const Act& hb = act[pl.hbuf];
   L2.out = hb.base; L2.out_pad = 0; L2.out_cs = hb.cs; L2.out_coff = 0;
   L2.hpool = 1;
-  if (!(pl.C == L2.cout && x3_rgb_fits(L1) && x3_hpool_ok(L2) && x3_c12_fits(L1, L2))) return 0;
+  if (!(pl.C == L2.cout && x3_rgb_fits(L1) && x3_hpool_ok(L2, cus, sw) && x3_c12_fits(L1, L2))) return 0;
   // the whole pool in the epilogue: the pooled buffer is the floor-mode 2x2 pool of conv1_2's
   // plane, written from its channel 0
   const Act& po = act[pl.out];
@@ -968,14 +942,16 @@ struct Step {
   Kind kind = POOL;
   int op = 0, nops = 1;      // the first op and how many the step covers
   ConvLaunch L{}, L2{};      // the launch (C12: conv1_1 and conv1_2), but for the split-K workspace and fold pointers
-  int code[3] = {0, 0, 0};   // op_variant of the covered ops (the first: X3, X3_RGB, PAIR report x3_last_variant())
+  X3Choice choice{};         // X3, X3_RGB, PAIR: what the launch runs (x3_choose)
+  int code[3] = {0, 0, 0};   // op_variant of the covered ops (the first of X3, X3_RGB, PAIR: the choice's code)
   int late_pool = -1;        // a deferred pool this conv has no pooled-input variant for: its vpool2 runs first
   bool covered = false;      // the step has an fp16-storage form (ISL_ACT_FP16)
   const char* error = nullptr;   // ISL_E_STATE: the run cannot take this step
 };
 
 // The launch plan of a run on the geometry `act`: what every op becomes, in order, with its
-// launch filled in.  A pure host function of its arguments and the ISLPOSE_* switches -- the run
+// launch filled in.  A pure host function of its arguments, the device's CU count and the
+// ISLPOSE_* switches, which it reads once (x3_switches) and returns in *sw_out -- the run
 // (run_ops_eager, on net->act) and the storage decision (act16_plan_ok, on a trial geometry
 // without addresses) both read it.  h16: ISL_PREC_FP16 (ISL_ALGO_X3 only), every x3 conv on the
 // one-term form of the variant the fp32 plan picks, from the hi-only packs -- the conv1_1 ->
@@ -984,14 +960,17 @@ struct Step {
 // holds fp16 between the convs, the launches are those of the fp32-storage run on the
 // fp16-storage forms.  far: the arena whose fold plan (plan_fold) applies, or null.
 static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& act, bool h16, bool a16,
-                                    const isl_net::Arena* far) {
+                                    const isl_net::Arena* far, X3Switches* sw_out = nullptr) {
+  const X3Switches sw = x3_switches();
+  if (sw_out) *sw_out = sw;
+  const int cus = device_cus();
   const size_t nops = net->ops.size();
   std::vector<Step> steps;
   steps.reserve(nops);
   bool fused = false;   // the previous conv wrote the pair-max buffer of this pool
   int vin_buf = -1;     // this conv stages from that buffer (the pool op was skipped)
-  const bool fuse_pools = fused_pool_enabled(), pool_input = fuse_pools && pool_input_enabled();
-  const int f67 = net->algo == ISL_ALGO_X3 ? fuse67_mode(h16) : 0;
+  const bool fuse_pools = fused_pool_enabled(sw), pool_input = fuse_pools && pool_input_enabled(sw);
+  const int f67 = net->algo == ISL_ALGO_X3 ? fuse67_mode(sw, h16) : 0;
   size_t perm_op = (size_t)-1;   // the pair (perm_op, perm_op + 1) runs as its permuted two launches
   // fp16 storage: the layer that writes a net output last also keeps the unrounded fp32 values
   auto store16 = [&](ConvLaunch& L, size_t writer) {
@@ -1008,7 +987,7 @@ static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& 
     Step& st = steps.back();
     ConvLaunch& L = st.L;
     st.op = (int)k;
-    const int form67 = vin_buf < 0 ? fuse67_form(net, act, k, f67) : 0;
+    const int form67 = vin_buf < 0 ? fuse67_form(net, act, k, f67, cus, sw) : 0;
     if (form67 == 2) perm_op = k;
     if (form67 == 1) {
       // Mconv6 -> Mconv7 in one launch (conv_x3 VAR 16): op k's input, op k + 1's output
@@ -1028,14 +1007,16 @@ static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& 
       st.nops = 2;
       st.code[1] = -2;   // ran inside op k
       // (the net input is fp32 in every arena: only the 3-channel kernel reads it)
-      st.covered = op.in != net->in_buf && x3_act16_ok(L);
+      st.choice = x3_choose(L, cus, sw);
+      st.code[0] = st.choice.code;
+      st.covered = op.in != net->in_buf && st.choice.act16;
       continue;
     }
 
     // conv1_1 (rgb kernel) -> conv1_2 -> pool: both convs and the pool in one launch writing the
     // pooled map (or, ISLPOSE_C12=2, the pool's pair-max buffer), where conv1_1's output feeds
     // conv1_2 only (conv_c12.hip; its fp16-storage form reads the fp32 net input)
-    const int form12 = vin_buf < 0 ? c12_form(net, act, k, fuse_pools, h16, a16, &st.L, &st.L2) : 0;
+    const int form12 = vin_buf < 0 ? c12_form(net, act, k, fuse_pools, h16, a16, cus, sw, &st.L, &st.L2) : 0;
     if (form12) {
       st.kind = Step::C12;
       st.nops = form12 == 2 ? 3 : 2;   // 2: the pool ran inside op k too; 1: the pool op finds its pair-max buffer written
@@ -1070,7 +1051,7 @@ static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& 
       L.wpk = (const float*)c.pack(PK_WINO); L.bco = c.wbco;
       st.kind = Step::WINO;
 #ifdef ISLPOSE_DEV
-    } else if (net->algo == ISL_ALGO_X3 && owns_pack(c, PK_WINO_X3) && x3_wino_enabled() && vin_buf < 0) {
+    } else if (net->algo == ISL_ALGO_X3 && owns_pack(c, PK_WINO_X3) && x3_wino_enabled(sw) && vin_buf < 0) {
       L.wx3 = c.pack(PK_WINO_X3); L.wscale_inv = c.inv[PK_WINO_X3];
       st.kind = Step::WINO_X3;
 #endif
@@ -1079,7 +1060,7 @@ static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& 
         const Act& hb = act[net->ops[vin_buf].hbuf];
         ConvLaunch Lv = L;
         Lv.in = hb.base; Lv.in_cs = hb.cs; Lv.in_coff = 0; Lv.vin = 1;
-        if (x3_vin_ok(Lv) && !(rgb_layer(c) && x3_rgb_fits(L))) L = Lv;
+        if (x3_vin_ok(Lv, cus, sw) && !(rgb_layer(c) && x3_rgb_fits(L))) L = Lv;
         else st.late_pool = vin_buf;   // no variant: the pool after all
         vin_buf = -1;
       }
@@ -1095,14 +1076,14 @@ static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& 
       } else if (c.x3_wide) {   // 256-channel tiles, two pairs per step, where the grid is big enough
         ConvLaunch Lw = L;
         Lw.bco = 256;
-        if (x3_wide1(Lw)) { L.bco = 256; kind = PK_X3_WIDE; }
+        if (x3_wide1(Lw, cus, sw)) { L.bco = 256; kind = PK_X3_WIDE; }
       }
       L.wx3 = c.pack(kind, h16);
       if (h16) L.f16 = 1;
       if (a16) store16(L, k);
       // the next op pools this conv's output: write pair maxima to its half-width buffer
       if (k + 1 < nops && net->ops[k + 1].type == 1 && net->ops[k + 1].in == op.out && op.out_coff == 0 &&
-          net->ops[k + 1].C == c.cout && fuse_pools && x3_hpool_ok(L)) {
+          net->ops[k + 1].C == c.cout && fuse_pools && x3_hpool_ok(L, cus, sw)) {
         const Act& hb = act[net->ops[k + 1].hbuf];
         L.out = hb.base; L.out_pad = 0; L.out_cs = hb.cs; L.out_coff = 0;
         L.hpool = 1;
@@ -1117,19 +1098,23 @@ static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& 
       ConvLaunch Lw = L;
       Lw.wx3 = c.pack(PK_WINO_F16);
       Lw.wscale_inv = c.inv[PK_WINO_F16];
-      if (!h16 && !perm && !pool_side && w2_enabled(L) && owns_pack(c, PK_WINO_F16) && !L.vin && !L.hpool && !folds &&
-          x3_split_ranges(L, nullptr) <= 1 && wino_f16_fits(Lw)) {
+      if (!h16 && !perm && !pool_side && w2_enabled(sw, L) && owns_pack(c, PK_WINO_F16) && !L.vin && !L.hpool && !folds &&
+          x3_split_ranges(L, nullptr, cus, sw) <= 1 && wino_f16_fits(Lw)) {
         L = Lw;
         st.kind = Step::W2;
         st.code[0] = x3_variant_code(X3V_W2, 3, 128, 64);
-      } else if (rgb_layer(c) && x3_rgb_fits(L) && rgb_kernel_enabled() && !L.vin) {
+      } else if (rgb_layer(c) && x3_rgb_fits(L) && rgb_kernel_enabled(sw) && !L.vin) {
         L.wx3 = c.pack(PK_RGB, h16);
         st.kind = Step::X3_RGB;
+        st.choice = x3_choose_rgb(L);
+        st.code[0] = st.choice.code;
         st.covered = true;
       } else {
         // (the net input is fp32 in every arena: only the 3-channel kernel reads it)
         st.kind = Step::X3;
-        st.covered = !folds && op.in != net->in_buf && x3_act16_ok(L);
+        st.choice = x3_choose(L, cus, sw);
+        st.code[0] = st.choice.code;
+        st.covered = !folds && op.in != net->in_buf && st.choice.act16;
       }
     } else {
       st.kind = Step::DIRECT;
@@ -1146,7 +1131,7 @@ static std::vector<Step> plan_steps(const isl_net* net, const std::vector<Act>& 
 static bool act16_plan_ok(const isl_net* net, const std::vector<Act>& geo) {
   if (fold_enabled()) return false;
 #ifdef ISLPOSE_DEV
-  if (x3_wino_enabled()) return false;
+  if (x3_wino_enabled(x3_switches())) return false;
 #endif
   for (const Step& st : plan_steps(net, geo, true, true, nullptr))
     if (!st.covered) return false;
@@ -1170,6 +1155,7 @@ static int plan_fold(isl_net* net, hipStream_t s) {
   ar.fold_n = net->pn;
   ar.fold_mode = mode;
   if (!mode) return ISL_OK;
+  const X3Switches fsw = x3_switches();
   auto is_conv_x3 = [&](size_t k) { return net->ops[k].type == 0 && x3_fits(basic_launch(net, net->act, net->ops[k])); };
   // a consumer may fold only on the generic loop with no pool on either side
   auto consumer_ok = [&](size_t j) {
@@ -1179,7 +1165,7 @@ static int plan_fold(isl_net* net, hipStream_t s) {
     if (j + 1 < nops && net->ops[j + 1].type == 1 && net->ops[j + 1].in == op.out) return false;
     const ConvLayer& c = net->layers[op.layer];
     if (rgb_layer(c)) return false;
-    return x3_fold_ok(basic_launch(net, net->act, op));
+    return x3_fold_ok(basic_launch(net, net->act, op), device_cus(), fsw);
   };
   struct Prod { size_t k; int S; long long off; std::vector<size_t> cons; };
   std::vector<Prod> prods;
@@ -1191,7 +1177,7 @@ static int plan_fold(isl_net* net, hipStream_t s) {
     if (c.cout % 8 || rgb_layer(c)) continue;
     ConvLaunch L = basic_launch(net, net->act, op);
     bool across = false;
-    const int S = x3_split_ranges(L, &across);
+    const int S = x3_split_ranges(L, &across, device_cus(), fsw);
     if (S < 2 || !across) continue;
     const int lo = op.out_coff, hi = op.out_coff + c.cout;
     auto overlaps = [&](const OutRef& o) { return o.buf == op.out && o.coff < hi && o.coff + o.C > lo; };
@@ -1288,10 +1274,8 @@ static int record_step(const isl_net* net, isl_net::TimedRun* tr, const Step& st
 #endif
     case Step::DIRECT: kind = 1; mf = conv_mfma_flops(L); break;
     case Step::WINO: kind = 2; mf = wino_mfma_flops(L); break;
-    case Step::X3: mf = conv_x3_mfma_flops(L); break;
-    case Step::X3_RGB: mf = conv_x3_rgb_mfma_flops(L); break;
+    case Step::X3: case Step::X3_RGB: case Step::PAIR: mf = st.choice.mfma_flops; break;
     case Step::W2: kind = 5; mf = wino_f16_mfma_flops(L); break;
-    case Step::PAIR: mf = conv_x3_fused67_mfma_flops(L); break;
     case Step::C12: mf = conv_x3_c12_mfma_flops(L); break;
   }
   for (int j = 0; j < st.nops; ++j) {
@@ -1327,7 +1311,8 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
   // ISL_ACT_FP16: the arena of this plan holds fp16 between the convs (plan() found every step covered)
   const bool a16 = ar.a16;
   if (a16 && !h16) return fail(ISL_E_STATE, "fp16 activation storage: the arena of this plan needs ISL_ALGO_X3 with ISL_PREC_FP16");
-  std::vector<Step> steps = plan_steps(net, net->act, h16, a16, &ar);
+  X3Switches sw;
+  std::vector<Step> steps = plan_steps(net, net->act, h16, a16, &ar, &sw);
   for (Step& st : steps) {
     const size_t k = st.op;
     const Op& op = net->ops[k];
@@ -1339,9 +1324,19 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
       HIP_OK(launch_vpool2(net->act[pool.hbuf], net->act[pool.out], pool.C, s));
       net->op_variant[st.late_pool] = 0;
     }
-    if (st.kind == Step::X3 || st.kind == Step::X3_RGB) {
+    if (st.kind == Step::X3) {
       // the split-K workspace and the fold pointers: allocations of this arena
-      const size_t need = x3_splitk_ws_floats(L);
+      if (ar.fold_ws_off[k] >= 0 || ar.fold_tab_off[k] >= 0) {
+        // a fold producer keeps its partial sums, a fold consumer reads such: another kernel
+        if (ar.fold_ws_off[k] >= 0) L.fold_out = 1;
+        if (ar.fold_tab_off[k] >= 0) {
+          if (L.vin || L.hpool || !x3_fold_ok(L, device_cus(), sw)) return fail(ISL_E_STATE, "split-K fold: consumer off the generic loop");
+          L.fold = ar.fold_tab + ar.fold_tab_off[k];
+        }
+        st.choice = x3_choose(L, device_cus(), sw);
+        st.code[0] = st.choice.code;
+      }
+      const size_t need = st.choice.ws_floats;
       if (need > ar.ks_floats) {
         if (net->capturing) return fail(ISL_E_STATE, "graph capture: split-K workspace growth");
         drop_graphs(ar);   // they name the old workspace
@@ -1354,17 +1349,13 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
       }
       L.ws = ar.ks;
       L.ws_floats = ar.ks_floats;
-      if (ar.fold_ws_off[k] >= 0) {   // a fold producer: its own partial-sum region, no reduce
+      if (L.fold_out) {   // a fold producer: its own partial-sum region, no reduce
         L.ws = ar.fold_mem + ar.fold_ws_off[k];
         L.ws_floats = need;
-        L.fold_out = 1;
-      }
-      if (ar.fold_tab_off[k] >= 0) {   // a fold consumer
-        if (L.vin || L.hpool || !x3_fold_ok(L)) return fail(ISL_E_STATE, "split-K fold: consumer off the generic loop");
-        L.fold = ar.fold_tab + ar.fold_tab_off[k];
       }
     }
     for (int j = 0; j < st.nops; ++j) net->op_variant[k + j] = st.code[j];
+    if (L.fold_out) net->op_variant[k] |= X3V_FOLD_OUT;
     switch (st.kind) {
       case Step::POOL: HIP_OK(launch_maxpool2(net->act[op.in], net->act[op.out], op.C, s)); break;
       case Step::VPOOL: HIP_OK(launch_vpool2(net->act[op.hbuf], net->act[op.out], op.C, s)); break;
@@ -1373,14 +1364,12 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
       case Step::W2: HIP_OK(launch_wino_f16(L, s)); break;
       case Step::C12: HIP_OK(launch_conv_x3_c12(L, st.L2, s)); break;
       case Step::X3_RGB: HIP_OK(launch_conv_x3_rgb(L, s)); break;
-      case Step::X3: case Step::PAIR: HIP_OK(launch_conv_x3(L, s)); break;
+      case Step::X3: case Step::PAIR: HIP_OK(launch_conv_x3(L, st.choice, sw, s)); break;
       case Step::DIRECT: HIP_OK(launch_conv(L, s)); break;
 #ifdef ISLPOSE_DEV
       case Step::WINO_X3: HIP_OK(launch_wino_x3(L, s)); break;
 #endif
     }
-    if (st.kind == Step::X3 || st.kind == Step::X3_RGB || st.kind == Step::PAIR)
-      net->op_variant[k] = x3_last_variant() | (L.fold_out ? X3V_FOLD_OUT : 0);
     if (tr)
       if (const int rc = record_step(net, tr, st, s)) return rc;
   }
@@ -1396,27 +1385,20 @@ static int run_ops_eager(isl_net* net, hipStream_t s) {
 // launches it on the caller's stream; later runs replay it.  The kernels, their order and
 // arguments are those of the eager run: the same bits.  Timed runs (isl_net_set_timing) and
 // the split-K fold (its plan uploads a table) stay eager.
-// The switches the launch selection of this build reads (its kernel choice per launch), in a
-// fixed order, each hashed as name=value; -- so the key depends on their values only, not on
-// the order of environ or on unrelated ISLPOSE_* variables.
-static const char* const kRunKeySwitches[] = {
-    "ISLPOSE_X3_DEEP",   "ISLPOSE_RGB_CONV", "ISLPOSE_FUSED_POOL", "ISLPOSE_POOL_INPUT", "ISLPOSE_CONV_STAGING",
-    "ISLPOSE_X3_TILES",  "ISLPOSE_X3_UNION", "ISLPOSE_X3_HALF64",  "ISLPOSE_X3_WIDE7",   "ISLPOSE_X3_ACROSS",
-    "ISLPOSE_X3_S8",     "ISLPOSE_X3_FUSE67", "ISLPOSE_X3_G2", "ISLPOSE_X3_PX64", "ISLPOSE_X3_HALFSMALL",
-    "ISLPOSE_X3_WR",     "ISLPOSE_X3_WR_WN", "ISLPOSE_C12",        "ISLPOSE_X3_TAIL",    "ISLPOSE_X3_SMALL7",
-    "ISLPOSE_X3_W2",     "ISLPOSE_X3_S7W96", "ISLPOSE_A16_DMA",
-#ifdef ISLPOSE_DEV
-    "ISLPOSE_X3_HALFCO", "ISLPOSE_X3_PPS2",  "ISLPOSE_X3_M16",     "ISLPOSE_X3_WINO",    "ISLPOSE_X3_ABL",
-#endif
-};
-
+// The switches the launch selection of this build reads (x3_switch_table: its run_key rows), in
+// table order, each hashed as name=value; -- so the key depends on their values only, not on the
+// order of environ or on unrelated ISLPOSE_* variables.
 static unsigned long long run_key(const isl_net* net) {
   unsigned long long h = 1469598103934665603ull;
   auto mix = [&](unsigned long long v) { h = (h ^ v) * 1099511628211ull; };
   mix((unsigned long long)net->pn);
   mix((unsigned long long)net->split_k + 16 * (unsigned long long)net->algo + 256 * (unsigned long long)net->precision +
       4096 * (unsigned long long)(net->cur && net->cur->a16 ? 1 : 0));
-  for (const char* name : kRunKeySwitches) {
+  int nsw = 0;
+  const X3SwitchDef* defs = x3_switch_table(&nsw);
+  for (int i = 0; i < nsw; ++i) {
+    if (!defs[i].run_key) continue;
+    const char* name = defs[i].name;
     const char* v = getenv(name);
     for (const char* c = name; *c; ++c) mix((unsigned char)*c);
     mix('=');
@@ -2245,20 +2227,21 @@ int isl_debug_conv(const isl_debug_conv_desc* dp, const float* x, const float* w
   L.allow_split = d.allow_split;
   L.vin = d.vin;
   // the choices plan_steps makes for a launch, in its order; the shape checks need no device memory
+  const X3Switches sw = x3_switches();
   int kind = PK_DIRECT;
   if (x3) {
     if (!x3_fits(L)) return bad("shape does not fit conv_x3");
-    if (d.vin && !x3_vin_ok(L)) return bad("no pooled-input variant for this launch (x3_vin_ok)");
+    if (d.vin && !x3_vin_ok(L, device_cus(), sw)) return bad("no pooled-input variant for this launch (x3_vin_ok)");
     ConvLaunch Lw = L;
     Lw.bco = 256;
-    if (x3_wide1_layer(d.ks, d.cout, cin_phys) && x3_wide1(Lw)) L.bco = 256;
+    if (x3_wide1_layer(d.ks, d.cout, cin_phys) && x3_wide1(Lw, device_cus(), sw)) L.bco = 256;
     L.f16 = d.f16;
     if (d.act16) {
-      if (!x3_act16_ok(L)) return bad("no fp16-storage form of this launch (x3_act16_ok)");
+      if (!x3_act16_ok(L, device_cus(), sw)) return bad("no fp16-storage form of this launch (x3_act16_ok)");
       L.act16 = 1;
     }
     if (d.hpool) {
-      if (!x3_hpool_ok(L)) return bad("no pair-max epilogue for this launch (x3_hpool_ok)");
+      if (!x3_hpool_ok(L, device_cus(), sw)) return bad("no pair-max epilogue for this launch (x3_hpool_ok)");
       L.hpool = 1;
     }
     kind = L.bco == 256 ? PK_X3_WIDE : PK_X3;
@@ -2302,7 +2285,8 @@ int isl_debug_conv(const isl_debug_conv_desc* dp, const float* x, const float* w
     L.bias = d_b; L.slope = d_s; L.range_flag = d_flag;
     if (pk.f16.empty()) L.wpk = (const float*)d_w; else L.wx3 = d_w;
     if (x3) {
-      const size_t need = x3_splitk_ws_floats(L);
+      const X3Choice ch = x3_choose(L, device_cus(), sw);
+      const size_t need = ch.ws_floats;
       if (need > (64u << 20)) return bad("split-K workspace over 256 MiB");
       if (need) {   // partial sums: a NaN where a reduce reads what no block wrote
         std::vector<uint32_t> hw(need, DBG_POISON32);
@@ -2310,11 +2294,11 @@ int isl_debug_conv(const isl_debug_conv_desc* dp, const float* x, const float* w
         HIP_OK(hipMemcpy(d_ws, hw.data(), need * 4, hipMemcpyHostToDevice));
         L.ws = d_ws; L.ws_floats = need;
       }
-      HIP_OK(launch_conv_x3(L, 0));
-      res->variant = x3_last_variant();
+      HIP_OK(launch_conv_x3(L, ch, sw, 0));
+      res->variant = ch.code;
     } else if (rgb) {
       HIP_OK(launch_conv_x3_rgb(L, 0));
-      res->variant = x3_last_variant();
+      res->variant = x3_choose_rgb(L).code;
     } else if (d.kernel == ISL_DBG_WINO2) {
       HIP_OK(launch_wino_f16(L, 0));
       res->variant = x3_variant_code(X3V_W2, 3, 128, 64);

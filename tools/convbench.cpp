@@ -82,7 +82,7 @@ int main(int argc, char** argv) {
   if (getenv("CONVBENCH_SPLIT")) {
     L.allow_split = atoi(getenv("CONVBENCH_SPLIT"));
     L.bco = bco;
-    L.ws_floats = x3_splitk_ws_floats(L);
+    L.ws_floats = x3_splitk_ws_floats(L, device_cus(), x3_switches());
     if (L.ws_floats) CK(hipMalloc(&L.ws, L.ws_floats * sizeof(float)));
   }
   // ISLPOSE_X3_UNION=4: s_memtime stamps of block 0 (16 waves x K steps x 4 points)
@@ -129,7 +129,7 @@ int main(int argc, char** argv) {
       pos = e + 1;
       ConvLaunch c = L;
       auto launch = [&]() -> hipError_t {
-        // x3m: the row union on 16x16x32 MFMAs (ISLPOSE_X3_M16=1, read per launch); x3: off
+        // x3m: the row union on 16x16x32 MFMAs (ISLPOSE_X3_M16=1; the switches are read per launch); x3: off
         // x3h: small grids on two 64-channel blocks per 128-channel tile (ISLPOSE_X3_HALFCO=1)
         // x3p: small grids with two chunk pairs per K step (ISLPOSE_X3_PPS2=1)
         // x3d: small grids with inputs and weights two K steps ahead (ISLPOSE_X3_DEEP=1)
@@ -139,14 +139,14 @@ int main(int argc, char** argv) {
           setenv("ISLPOSE_X3_HALFCO", a == "x3h" ? "1" : "0", 1);
           setenv("ISLPOSE_X3_PPS2", a == "x3p" ? "1" : "0", 1);
           c.bco = bco; c.wpk = wd;
-          return launch_conv_x3(c, 0);
+          return launch_conv_x3(c, x3_switches(), 0);
         }
         // x3f: the fused 1x1 pair (cout = Mconv6 channels; CONVBENCH_F7 Mconv7 outputs, default 52)
         if (a == "x3f" && ks == 1) {
           c.cout7 = getenv("CONVBENCH_F7") ? atoi(getenv("CONVBENCH_F7")) : 52;
           c.wx3f7 = f7w; c.bias7 = bias; c.slope7 = slope; c.act7 = ACT_PRELU; c.wscale7_inv = 1.f / 16384.f;
           c.out_cs = 64; c.bco = cout; c.wpk = wd;
-          return launch_conv_x3(c, 0);
+          return launch_conv_x3(c, x3_switches(), 0);
         }
         if (a == "direct") { c.bco = bco; c.wpk = wd; return launch_conv(c, 0); }
         if (a == "wino" && wb && ks == 3) { c.bco = wb; c.wpk = wu; return launch_wino(c, 0); }
@@ -180,7 +180,7 @@ int main(int argc, char** argv) {
         // before every timed launch, as in the net, where kernels of other shapes alternate
         for (int i = 0; i < iters; ++i) {
           if (flush) CK(hipMemsetAsync(flush, i & 0xff, flush_bytes, 0));
-          if (pollute) CK(launch_conv_x3(PL, 0));
+          if (pollute) CK(launch_conv_x3(PL, x3_switches(), 0));
           CK(hipEventRecord(e0, 0));
           CK(launch());
           CK(hipEventRecord(e1, 0));
