@@ -9,7 +9,7 @@ OUT      := $(PKG)/islpose/libislpose.so
 # operation order bit-for-bit, which forbids fused multiply-adds.
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -Iinclude -I$(CSRC) \
             -Wall -Wno-unused-function -Wno-unused-variable -Wno-unused-lambda-capture
-SRCS     := $(CSRC)/conv.hip $(CSRC)/conv_x3.hip $(CSRC)/conv_c12.hip $(CSRC)/wino_f16.hip $(CSRC)/wino.hip $(CSRC)/ops.hip $(CSRC)/post.hip $(CSRC)/sign.hip $(CSRC)/sign_train.hip $(CSRC)/augment.hip $(CSRC)/draw.hip $(CSRC)/pack.cpp $(CSRC)/x3_select.cpp $(CSRC)/runtime.cpp
+SRCS     := $(CSRC)/conv.hip $(CSRC)/conv_x3.hip $(CSRC)/conv_c12.hip $(CSRC)/wino_f16.hip $(CSRC)/wino.hip $(CSRC)/ops.hip $(CSRC)/post.hip $(CSRC)/sign.hip $(CSRC)/sign_train.hip $(CSRC)/augment.hip $(CSRC)/draw.hip $(CSRC)/pack.cpp $(CSRC)/x3_select.cpp $(CSRC)/post_plan.cpp $(CSRC)/runtime.cpp
 OBJS     := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 # development objects (tools/convbench): the product sources plus the rejected split-fp16
 # Winograd kernel and the s_memtime stamp variant, compiled with -DISLPOSE_DEV
@@ -19,6 +19,9 @@ DEV_OBJS := $(patsubst $(CSRC)/%,build_dev/%.o,$(DEV_SRCS))
 all: $(OUT)
 
 HDRS     := $(CSRC)/internal.h $(CSRC)/x3_select.h $(CSRC)/pack.h $(CSRC)/sign_common.h include/islpose.h
+
+# (post_plan.h: the sizing constants, switches, plans and scratch layouts of the post)
+build/post.hip.o build/post_plan.cpp.o build_dev/post.hip.o build_dev/post_plan.cpp.o: $(CSRC)/post_plan.h
 
 # (x3_instances.h: the instance table of the split-fp16 kernels and its host-side copy)
 build/conv_x3.hip.o build/x3_select.cpp.o build_dev/conv_x3.hip.o build_dev/x3_select.cpp.o: $(CSRC)/x3_instances.h
@@ -55,3 +58,8 @@ tools/pack_digest: tools/pack_digest.cpp $(CSRC)/pack.cpp $(CSRC)/pack.h
 # under the decision (tests/test_x3_select.py): host compiler only, no device
 tools/x3_choice: tools/x3_choice.cpp $(CSRC)/x3_select.cpp $(CSRC)/x3_select.h $(CSRC)/x3_instances.h
 	$(HOSTCXX) -O2 -std=c++17 -ffp-contract=off -Wall -I$(CSRC) tools/x3_choice.cpp $(CSRC)/x3_select.cpp -o $@
+
+# the plans and scratch layouts of the post-processing for a geometry (tests/test_post_plan.py):
+# host compiler only, no device
+tools/post_plan: tools/post_plan.cpp $(CSRC)/post_plan.cpp $(CSRC)/post_plan.h include/islpose.h
+	$(HOSTCXX) -O2 -std=c++17 -ffp-contract=off -Wall -Iinclude -I$(CSRC) tools/post_plan.cpp $(CSRC)/post_plan.cpp -o $@

@@ -447,7 +447,9 @@ typedef struct {
   isl_resize_plan stage1[ISL_PLAN_SCALES];    /* x8 to the valid size (two-stage scales only)   */
   isl_resize_plan final_rs[ISL_PLAN_SCALES];  /* the resize that lands on the frame; launched   */
                                               /* only for a single scale that is not fused      */
-  int32_t reserved[6];
+  int32_t env_limb_lds;     /* ISLPOSE_LIMB_LDS: large pair sets ranked and matched in LDS      */
+  int32_t env_asm_reg;      /* ISLPOSE_ASM_REG: the assembly's merge in registers               */
+  int32_t reserved[4];
 } isl_body_post_plan;
 
 typedef struct {

@@ -27,6 +27,7 @@
 
 #include "internal.h"
 #include "islpose.h"
+#include "post_plan.h"
 
 namespace isl {
 
@@ -122,7 +123,7 @@ __device__ __forceinline__ float sample(const MapSrc& m, int f, int c, int y, in
 // horizontal pass is computed once per source row the tile needs (OpenCV's
 // HResizeCubic, stored in LDS), then every output combines 4 of those rows
 // (VResizeCubic) -- the same values OpenCV computes, with 4-5x fewer loads.
-constexpr int RS_TY = 64, RS_TX = 256, RS_MAXR = 40;   // 64 rows: amortise the horizontal pass
+// (RS_TY = 64 rows: amortise the horizontal pass; RS_TX, RS_MAXR, BM_ROWS: post_plan.h)
 // The vertical taps of the tile's output rows are computed once per block into LDS (they
 // depend on the row only; per thread they were most of the vertical pass's VALU work), and
 // the block is TX = 128 or 256 columns wide, whichever wastes fewer idle lanes on the
@@ -135,7 +136,6 @@ constexpr int RS_TY = 64, RS_TX = 256, RS_MAXR = 40;   // 64 rows: amortise the 
 // V4 (mode 1, TX = 128, not identity, ow % 4 == 0): the vertical pass by 4 adjacent columns x
 // ty/4 rows per thread -- ds_read_b128 of the 4 LDS rows, one 16-byte store per output row (the
 // HBM write path wants 16 bytes per lane) -- and with BM one band per thread (ty = 64).
-constexpr int BM_ROWS = 16;
 template <int TX, int VU = 1, int HU = 8, bool BM = false, bool V4 = false>
 __global__ void __launch_bounds__(TX) resize_sep_kernel(MapSrc m, int nch, int oh, int ow, int ty_rows, int mode,
                                                          float inv_div_f, void* out, float* bandmax = nullptr,
@@ -278,7 +278,7 @@ __global__ void __launch_bounds__(TX) resize_sep_kernel(MapSrc m, int nch, int o
 // LDS, vertical combine) and heatmap_avg += heatmap / len(multiplier) in scale order in
 // fp64 registers, one store.  The same bits as a mode-(3|8) pass then ns-1 mode-3 passes,
 // without their ns read-modify-write sweeps of the fp64 average.
-constexpr int RA_TY = 16;   // output rows per block (fp64 accumulators in registers)
+// (RA_TY output rows per block, fp64 accumulators in registers: post_plan.h)
 struct MapSrcN {   // up to MAX_SCALES (8) scales
   MapSrc m[8];
 };
@@ -380,7 +380,7 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
 //   axis 1: one thread per 14-column run of one of the 18 rows, 38 v values in
 //           registers -> g into LDS
 //   NMS:    one wave per (row, 64-column word), ballot -> mask word.
-constexpr int NMS_TY = 16, NMS_TX = 192, NMS_R = 12;
+constexpr int NMS_R = 12;                          // (NMS_TY, NMS_TX: post_plan.h)
 constexpr int NMS_VR = NMS_TY + 2;                 // g / v rows (1-px ring)
 constexpr int NMS_VC = NMS_TX + 2 + 2 * NMS_R;     // v columns (218)
 constexpr int NMS_GC = NMS_TX + 2;                 // g columns (194)
@@ -391,13 +391,11 @@ constexpr int NMS_SEG = 14;                        // g outputs per thread in th
 // tile's input window is resized on the fly from the low-resolution map `m`
 // (stage-1 cv2.resize x8, cropped: body.py:68-73 when the net input is the frame),
 // with resize_sep_kernel's exact operation order.  Only scale 1/8 is fused.
-constexpr int NMS_SRC_ROWS = 16;
-constexpr int NMS_SRC_COLS = 48;                   // source columns (218 / 8 + 5 = 33 at scale 1/8; 42 at 1/5.9)
+// (the window: NMS_SRC_ROWS x NMS_SRC_COLS, post_plan.h)
 // The wide window (Mode R at 368 x 656: the stage-2 resize is x2, a tile reads ~26 x 114 source
 // values): 72 KB of LDS per block, two blocks per CU, against writing and re-reading 0.8 GB of
-// full-resolution heat planes per 32 frames -- measured slower, opt-in (fused_wide_enabled).
-constexpr int NMS_WSRC_ROWS = 28;
-constexpr int NMS_WSRC_COLS = 120;
+// full-resolution heat planes per 32 frames -- measured slower, opt-in (ISLPOSE_FUSED_WIDE):
+// NMS_WSRC_ROWS x NMS_WSRC_COLS, post_plan.h.
 
 // [min, max] of reflect_idx(i, n) over i in [lo, hi]
 __device__ __forceinline__ void reflect_range(int lo, int hi, int n, int* a, int* b) {
@@ -1015,23 +1013,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof
   }
 }
 
-// ISLPOSE_BLUR_EXACT=1: every live tile on the fp64 passes, without the fp32 filter; =2: the
-// filter with a margin so wide that nearly every live tile falls back (A/B and the filter's
-// tests: the same mask bits either way; per call)
-static int blur_exact_only() {
-  const char* e = getenv("ISLPOSE_BLUR_EXACT");
-  return e && (e[0] == '1' || e[0] == '2') ? e[0] - '0' : 0;
-}
-
 // The blur of one post: the filter launch, then the exact passes over the tiles it could
-// not decide (a grid-stride launch over its list; ISLPOSE_BLUR_EXACT=1: the exact passes
-// over every tile instead).  `grid` / `live`: one tile per block or a live list (as
-// blur_nms_kernel); amb: n_tiles + 1 ints of scratch.
+// not decide (a grid-stride launch over its list; ex = 1: the exact passes over every tile
+// instead; ex = 2: the filter with a margin so wide that nearly every live tile falls back --
+// ISLPOSE_BLUR_EXACT as the caller read it).  `grid` / `live`: one tile per block or a live list
+// (as blur_nms_kernel); amb: n_tiles + 1 ints of scratch.
 template <typename T, bool FUSED, int WR = NMS_SRC_ROWS, int WC = NMS_SRC_COLS>
 static int launch_blur(dim3 grid, hipStream_t s, const T* planes, int H, int W, int words, unsigned long long* mask,
                        double thre, int mode_hand, const MapSrc& m, int nch, const int* live, const int* live_count,
-                       int tiles_x, int tiles_y, const float* bandmax, int* amb, bool amb_zeroed = false) {
-  const int ex = blur_exact_only();
+                       int tiles_x, int tiles_y, const float* bandmax, int* amb, int ex, bool amb_zeroed = false) {
   if (ex == 1) {
     hipLaunchKernelGGL((blur_nms_kernel<T, FUSED, true, WR, WC>), grid, dim3(256), 0, s, planes, H, W, words, mask,
                        thre, mode_hand, m, nch, live, live_count, tiles_x, tiles_y, bandmax, nullptr, nullptr, 0);
@@ -1245,7 +1235,6 @@ __global__ void __launch_bounds__(256) compact_kernel(const unsigned long long* 
 // PAF scoring + greedy matching + assembly (body.py:128-235), one block per frame
 // ---------------------------------------------------------------------------
 
-constexpr int MAX_SCALES = 8;
 static_assert(sizeof(MapSrcN::m) / sizeof(MapSrc) == MAX_SCALES, "resize_acc_kernel takes every scale");
 
 struct GroupArgs {
@@ -1698,11 +1687,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) l
 // lives in LDS when it fits (`in_lds`), so the row scans of the greedy merge are
 // LDS ballots instead of dependent global loads; the kept rows are written to
 // the record in one pass at the end.
-constexpr int ASM_LDS_ROWS = 256;   // subset rows that fit the LDS table (256 x 27 doubles = 55 KB)
+// (ASM_LDS_ROWS subset rows fit the LDS table: post_plan.h)
 // The frame's connections and the candidate scores the merge adds are staged in LDS first, all
 // lanes loading at once (ASM_CONN_CACHE of them; more: read in place): the serial merge then
 // never waits on a global load (it waited on two per connection, ~75 us per 32-frame batch).
-constexpr int ASM_CONN_CACHE = 512;   // x 5 doubles = 20 KB
 // The merge with the table in registers: lane r holds subset row r, the limbs unrolled at compile
 // time so that row[A] / row[B] are fixed registers.  The common connections -- one hit (a
 // predicated update in the hit lane) or none (a new row) -- are then two compares and a ballot,
@@ -2329,18 +2317,8 @@ __device__ double np_sum(const double* a, int n) {
   return s;
 }
 
-constexpr int CC_LDS_MAX = 36864;   // plane pixels whose parent array fits LDS (144 KB)
-constexpr int CC_CHUNK = 4096;      // pixels per row chunk of the large-plane path
-constexpr int CC_WMAX = 8192;       // widest plane the large-plane path takes (LDS chunk parents)
-constexpr int CC_MAXC = 64;         // candidate components kept per plane
-
-// per-plane results of the large-plane pre-pass
-struct CcStats {
-  int count;                        // foreground pixels
-  int ncand;                        // components whose approximate sum reaches the candidate bar
-  unsigned long long maxbits;       // largest approximate component sum (bits of a positive double)
-  int cand[CC_MAXC];                // their roots, unordered
-};
+// (CC_LDS_MAX, CC_CHUNK, CC_WMAX, CC_MAXC and CcStats, the per-plane results of the large-plane
+// pre-pass: post_plan.h)
 
 // Adds map[p] into vals[root of p] for p in [p0, p1): runs of equal roots are summed
 // in a register and flushed with one atomic; the last flush of a wave whose lanes all
@@ -2615,13 +2593,7 @@ __global__ void __launch_bounds__(256) cc_cand_kernel(int h, int w, int rows, in
 // per (plane, chunk) the candidates' pixel counts and first maxima (cc_count), then
 // their values compacted in raster order into `vals` (cc_scatter, each chunk at the
 // prefix of the counts before it), so the per-plane kernel only runs numpy's
-// pairwise sums and reduces the chunk maxima.
-constexpr int CC_KFAST = 4;
-struct CcChunk {
-  int count[CC_KFAST];
-  int besti[CC_KFAST];
-  double bestv[CC_KFAST];
-};
+// pairwise sums and reduces the chunk maxima.  (CC_KFAST, CcChunk: post_plan.h)
 
 __device__ __forceinline__ void cc_pick2(double& v, int& i, double v2, int i2) {
   if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
@@ -3116,25 +3088,6 @@ extern "C" int isl_body_layout(int model_kind, const isl_caps* caps, isl_layout*
 }
 
 
-static bool fused_blur_enabled() {
-  const char* e = getenv("ISLPOSE_FUSED_BLUR");   // A/B switch (tests); default on
-  return !(e && e[0] == '0');
-}
-
-// ISLPOSE_FUSED_WIDE=1: two-stage frames whose stage-2 scale needs the wide LDS window
-// (Mode R at 368 x 656) resize on the fly in blur_nms too (A/B; per call).  Off by default:
-// measured slower than materialising the planes (Mode R batch-32 post 1.54 -> 1.61 ms, batch
-// 1 0.19 -> 0.22 ms, profiles/r03/wide/): two 72 KB blocks per CU and a 28-row horizontal
-// pass per tile cost more than the 0.8 GB write and re-read.
-#ifdef ISLPOSE_DEV
-static bool fused_wide_enabled() {
-  const char* e = getenv("ISLPOSE_FUSED_WIDE");
-  return e && e[0] == '1';
-}
-#else
-static bool fused_wide_enabled() { return false; }   // rejected: development build only
-#endif
-
 static int post_fail(int code, const char* msg) {
   set_error(msg);
   return code;
@@ -3149,35 +3102,6 @@ static int post_fail(int code, const char* msg) {
     }                                                       \
   } while (0)
 
-// rows per tile: `ty` lowered until the source window of a resize of vertical scale scy fits
-// the LDS rows
-static int fit_rows(int ty, double scy, bool identity) {
-  if (!identity)
-    while (ty > 1 && (ty - 1) * scy + 5.0 > (double)RS_MAXR) --ty;
-  return ty;
-}
-static int resize_rows(double scy, bool identity) {   // output rows per resize tile
-  return fit_rows(RS_TY, scy, identity);
-}
-static bool env_on(const char* name) {   // an A/B switch that is on unless set to 0 (read per call)
-  const char* e = getenv(name);
-  return !(e && e[0] == '0');
-}
-// The form launch_resize runs for a source of vertical scale scy onto ow columns; want_bm: the
-// caller has a band-maxima buffer for it (mode 1).  (ISLPOSE_RESIZE_V4=0: the one-column vertical
-// pass everywhere; A/B, per call)
-static isl_resize_plan resize_form(double scy, bool identity, int ow, int mode, bool want_bm) {
-  isl_resize_plan f{};
-  f.launched = 1;
-  f.identity = identity;
-  f.ty = resize_rows(scy, identity);
-  const bool v4 = mode == 1 && !identity && ow % 4 == 0 && f.ty % 4 == 0 && env_on("ISLPOSE_RESIZE_V4");
-  f.bm = want_bm && mode == 1 && f.ty % BM_ROWS == 0;
-  f.v4 = f.bm ? v4 && f.ty == 4 * BM_ROWS : v4;
-  // 128-column blocks unless 256 pads less (it never does); the BM and V4 forms are 128 wide
-  f.cols = f.bm || f.v4 || (ow + 127) / 128 * 128 <= (ow + RS_TX - 1) / RS_TX * RS_TX ? 128 : RS_TX;
-  return f;
-}
 // planar resize of n*nch planes (see resize_sep_kernel); rows per tile sized to the LDS window
 // bandmax (mode 1): also write the band maxima of the output planes (resize_sep_kernel BM) when
 // the tiles align with the bands; *bm_done says whether they were written
@@ -3249,10 +3173,9 @@ static int low_src(isl_net* net, const float* p, int which, int n, int C, int h8
 // device buffer of `tiles` x 10 u64 (zeroed here); isl_dev_tile_prof copies it out
 static unsigned long long* g_prof_buf = nullptr;
 static size_t g_prof_tiles = 0;
-static void tile_prof_arm(size_t tiles, hipStream_t s) {
-  const char* e = getenv("ISLPOSE_TILE_PROF");
+static void tile_prof_arm(size_t tiles, hipStream_t s, const PostSwitches& sw) {
   unsigned long long* p = nullptr;
-  if (e && e[0] == '1') {
+  if (sw.tile_prof) {
     if (tiles > g_prof_tiles) {
       if (g_prof_buf) (void)hipFree(g_prof_buf);
       g_prof_buf = nullptr;
@@ -3267,10 +3190,9 @@ static void tile_prof_arm(size_t tiles, hipStream_t s) {
 // ISLPOSE_ASM_PROF=1 (development build): assemble_kernel stamps its phases per frame
 static unsigned long long* g_asm_buf = nullptr;
 static size_t g_asm_frames = 0;
-static void asm_prof_arm(size_t frames, hipStream_t s) {
-  const char* e = getenv("ISLPOSE_ASM_PROF");
+static void asm_prof_arm(size_t frames, hipStream_t s, const PostSwitches& sw) {
   unsigned long long* p = nullptr;
-  if (e && e[0] == '1') {
+  if (sw.asm_prof) {
     if (frames > g_asm_frames) {
       if (g_asm_buf) (void)hipFree(g_asm_buf);
       g_asm_buf = nullptr;
@@ -3290,8 +3212,8 @@ extern "C" int isl_dev_tile_prof(void* host, size_t tiles) {
   return hipMemcpy(host, g_prof_buf, tiles * 10 * 8, hipMemcpyDeviceToHost) == hipSuccess ? ISL_OK : ISL_E_HIP;
 }
 #else
-static void tile_prof_arm(size_t, hipStream_t) {}
-static void asm_prof_arm(size_t, hipStream_t) {}
+static void tile_prof_arm(size_t, hipStream_t, const PostSwitches&) {}
+static void asm_prof_arm(size_t, hipStream_t, const PostSwitches&) {}
 #endif
 
 extern "C" int isl_post_opts_default(isl_post_opts* opts) {
@@ -3319,95 +3241,12 @@ static int post_opts_resolve(const isl_post_opts* opts, isl_post_opts* out, cons
   return ISL_OK;
 }
 
-static_assert(ISL_PLAN_SCALES == MAX_SCALES, "the plan structs hold one slot per scale");
-
-static bool plan_geom_ok(int nscales, const isl_scale_geom* geom) {
-  if (nscales <= 0 || nscales > MAX_SCALES || !geom) return false;
-  for (int si = 0; si < nscales; ++si)
-    if (geom[si].net_h < 8 || geom[si].net_w < 8 || geom[si].valid_h < 1 || geom[si].valid_w < 1) return false;
-  return true;
-}
-
-// What isl_body_post_opts chooses on the host for n frames of H x W (no device work): the
-// post launches from this plan, and isl_debug_body_post_plan returns it.
-static void body_post_plan(int kind, int n, int H, int W, int nscales, const isl_scale_geom* geom,
-                           isl_body_post_plan* p) {
-  memset(p, 0, sizeof(*p));
-  const int nlimbs = kind == ISL_BODY25 ? 24 : 19;
-  const isl_scale_geom& g0 = geom[0];
-  const bool multi = nscales > 1;
-  // single scale with the net input at frame size (one x8 resize): fuse resize + blur,
-  // no full-resolution heat planes
-  // single scale, two stages (Mode R on large frames: 184 x 327 -> 1080 x 1920): the
-  // second resize is a strong upsampling whose full-resolution planes cost more HBM
-  // traffic than the on-the-fly resize; fused too when a blur tile's source window fits
-  // the LDS window (~1/5.2 and below; at 368 x 656, scale 1/2, it does not)
-  // (the wide window takes stage-2 scales down to ~1/2: Mode R at 368 x 656)
-  auto window_fits = [&](int rows, int cols) {
-    return 41.0 * g0.valid_h / H + 6.0 <= rows && 217.0 * g0.valid_w / W + 6.0 <= cols;
-  };
-  const bool two = !multi && !(g0.valid_h == H && g0.valid_w == W);
-  const bool fuse2_small = two && window_fits(NMS_SRC_ROWS, NMS_SRC_COLS);
-  p->env_fused_wide = fused_wide_enabled();
-  p->env_fused_blur = fused_blur_enabled();
-  const bool fuse2 = two && (fuse2_small || (window_fits(NMS_WSRC_ROWS, NMS_WSRC_COLS) && p->env_fused_wide));
-  const bool fused = !multi && (!two || fuse2) && p->env_fused_blur;
-  p->multi = multi;
-  p->two_stage = two;
-  p->fuse2 = fuse2;
-  p->wide = fuse2 && !fuse2_small;
-  p->fused = fused;
-  // ISLPOSE_BLUR_LIST=0: the band-maxima early out inside every tile's block instead of a live
-  // list (A/B; per call)
-  p->env_blur_list = env_on("ISLPOSE_BLUR_LIST");
-  // single scale, materialised planes: the band maxima of the final resize (blur early out)
-  // (ISLPOSE_BLUR_BANDS=0: without, A/B; read per call)
-  p->env_blur_bands = env_on("ISLPOSE_BLUR_BANDS");
-  const bool bands = !fused && !multi && p->env_blur_bands;
-  // two-stage frames: stage-2 tiles that no live window reads are skipped (stage2_need_kernel;
-  // ISLPOSE_RESIZE_SKIP=0 off, A/B, per call), which takes the band-maxima V4 form of both stages
-  p->env_resize_skip = env_on("ISLPOSE_RESIZE_SKIP");
-  p->env_resize_v4 = env_on("ISLPOSE_RESIZE_V4");
-  p->env_blur_exact = blur_exact_only();
-  const double scy2 = 1.0 / ((double)H / g0.valid_h);
-  const isl_resize_plan s1bm = resize_form(1.0 / 8.0, false, g0.valid_w, 1, true);
-  const isl_resize_plan s2bm = resize_form(scy2, false, W, 1, true);
-  p->skip2 = !fused && !multi && two && bands && p->env_blur_list && p->env_resize_skip && s1bm.bm && s1bm.v4 &&
-             s2bm.bm && s2bm.v4;
-  p->stage2_ty = resize_rows(scy2, false);
-  int acc_ty = RA_TY;
-  for (int si = 0; si < nscales; ++si) {
-    const isl_scale_geom& g = geom[si];
-    const bool two_stage = !(g.valid_h == H && g.valid_w == W);
-    p->scale_two_stage[si] = two_stage;
-    // stage 1: cv2.resize(fx=fy=8); stage 2: cv2.resize(crop, (W, H)), scale = 1 / (H / valid_h)
-    if (two_stage) p->stage1[si] = resize_form(1.0 / 8.0, false, g.valid_w, 1, p->skip2);
-    const double scy = two_stage ? 1.0 / ((double)H / g.valid_h) : 1.0 / 8.0;
-    if (multi) acc_ty = fit_rows(acc_ty, scy, false);   // every scale's final resize, one fp64 pass
-    else if (!fused) p->final_rs[si] = resize_form(scy, false, W, 1, bands);
-  }
-  p->acc_ty = multi ? acc_ty : 0;
-  if (multi) p->blur = ISL_BLUR_MULTI_F64;
-  else if (fused) p->blur = ISL_BLUR_FUSED_LIVE;
-  else if (p->final_rs[0].bm && p->env_blur_list) p->blur = ISL_BLUR_BAND_LIVE;
-  else p->blur = ISL_BLUR_DENSE;
-  p->blur_bandmax = p->blur == ISL_BLUR_DENSE && p->final_rs[0].bm;
-  // a frame per call: the scoring over Z blocks per limb (MODE 1), then ranks and matches (MODE 2);
-  // ISLPOSE_LIMB_SPLIT=0: one block per limb (A/B; read per call)
-  // ISLPOSE_LIMB_Z=z: z blocks per limb (A/B; read per call).  A 1080p frame's scoring: 10 / 32 /
-  // 64 blocks per limb 70.7 / 34.5 / 40.5 us (profiles/r06/lk/lz/); each pair is scored whole
-  // by one block, so the slicing changes no sum
-  const char* lzs = getenv("ISLPOSE_LIMB_Z");
-  p->limb_z = !env_on("ISLPOSE_LIMB_SPLIT") || n * nlimbs >= 128 ? 1
-              : lzs ? std::max(1, std::min(64, atoi(lzs))) : std::max(1, std::min(32, 1024 / (n * nlimbs)));
-}
-
 extern "C" int isl_debug_body_post_plan(int model_kind, int n, int H, int W, int nscales, const isl_scale_geom* geom,
                                         isl_body_post_plan* out) {
   if ((model_kind != ISL_BODY25 && model_kind != ISL_COCO) || n <= 0 || H <= 0 || W <= 0 || !out ||
       !plan_geom_ok(nscales, geom))
     return post_fail(ISL_E_ARG, "isl_debug_body_post_plan: bad argument");
-  body_post_plan(model_kind, n, H, W, nscales, geom, out);
+  body_post_plan(model_kind, n, H, W, nscales, geom, post_switches(), out);
   return ISL_OK;
 }
 
@@ -3435,59 +3274,38 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
   int rc = isl_body_layout(kind, caps, &lay);
   if (rc) return rc;
   // ---- scratch plan ----
+  const PostSwitches sw = post_switches();   // read once per call
   isl_body_post_plan plan;  // every choice between kernel forms and blur branches (body_post_plan)
-  body_post_plan(kind, n, H, W, nscales, geom, &plan);
+  body_post_plan(kind, n, H, W, nscales, geom, sw, &plan);
   const bool multi = plan.multi, wide = plan.wide, fused = plan.fused, skip2 = plan.skip2;
-  const size_t heat_bytes = fused ? 0 : (size_t)n * nparts * H * W * (multi ? 8 : 4);
-  size_t mid_bytes = 0;
-  for (int si = 0; si < nscales; ++si) {
-    const isl_scale_geom& g = geom[si];
-    if (!(g.valid_h == H && g.valid_w == W)) mid_bytes += (size_t)n * g.valid_h * g.valid_w * nparts * 4;
-  }
   const int words = (W + 63) / 64;
-  const size_t mask_bytes = (size_t)n * nparts * H * words * 8;
-  const size_t pair_bytes = (size_t)n * nlimbs * caps->max_pairs * (8 + 4 + 4);
-  const size_t used_bytes = (size_t)n * nlimbs * 2 * caps->max_peaks;
-  const size_t n_tiles_all = (size_t)((W + NMS_TX - 1) / NMS_TX) * ((H + NMS_TY - 1) / NMS_TY) * n * nparts;
-  const bool band_list = plan.env_blur_list;
-  // single scale, materialised planes: the band maxima of the final resize (blur early out)
-  const size_t bm_bytes = (!fused && !multi && plan.env_blur_bands) ? (size_t)n * nparts * ((H + BM_ROWS - 1) / BM_ROWS) * words * 4 : 0;
-  const size_t live_bytes = (fused || (bm_bytes && band_list)) ? (n_tiles_all + 1) * sizeof(int) : 0;
-  const size_t amb_bytes = (n_tiles_all + 1) * sizeof(int);   // the filter's undecided tiles
-  // two-stage frames: stage-2 tiles that no live window reads are skipped (stage2_need_kernel).
-  // bm1: the stage-1 planes' band maxima
-  const isl_scale_geom& g0 = geom[0];
+  const BodyPostLayout sl = body_post_layout(plan, kind, n, H, W, nscales, geom, *caps);
+  const size_t n_tiles_all = sl.n_tiles;
+  // two-stage frames: stage-2 tiles that no live window reads are skipped (stage2_need_kernel)
   const int ty2 = plan.stage2_ty, ry_tiles = (H + ty2 - 1) / ty2, rx_tiles = (W + 127) / 128;
-  const size_t bm1_bytes = skip2 ? (size_t)n * nparts * ((g0.valid_h + BM_ROWS - 1) / BM_ROWS) * ((g0.valid_w + 63) / 64) * 4 : 0;
-  const size_t lmid_bytes = skip2 ? n_tiles_all : 0;
-  const size_t need_bytes = skip2 ? (size_t)n * nparts * ry_tiles * rx_tiles : 0;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t total = up(heat_bytes) + up(mid_bytes) + up(mask_bytes) + up(pair_bytes) + up(used_bytes) +
-                       up(live_bytes) + up(bm_bytes) + up(amb_bytes) + up(bm1_bytes) + up(lmid_bytes) +
-                       up(need_bytes);
-  char* base = (char*)net_scratch(net, total);
+  char* base = (char*)net_scratch(net, sl.total);
   if (!base) return ISL_E_HIP;
-  char* heat = base;
-  char* mid = heat + up(heat_bytes);
-  unsigned long long* mask = (unsigned long long*)(mid + up(mid_bytes));
-  char* pairs = (char*)mask + up(mask_bytes);
-  unsigned char* used = (unsigned char*)(pairs + up(pair_bytes));
-  int* live_count = (int*)(used + up(used_bytes));
+  char* heat = base + sl.heat.off;
+  char* mid = base + sl.mid.off;
+  unsigned long long* mask = (unsigned long long*)(base + sl.mask.off);
+  char* pairs = base + sl.pairs.off;
+  unsigned char* used = (unsigned char*)(base + sl.used.off);
+  int* live_count = (int*)(base + sl.live.off);
   int* live = live_count + 1;
-  float* bandmax = bm_bytes ? (float*)((char*)live_count + up(live_bytes)) : nullptr;
-  int* amb = (int*)((char*)live_count + up(live_bytes) + up(bm_bytes));
-  float* bm1 = skip2 ? (float*)((char*)amb + up(amb_bytes)) : nullptr;
-  unsigned char* live_mid = skip2 ? (unsigned char*)bm1 + up(bm1_bytes) : nullptr;
-  unsigned char* need = skip2 ? live_mid + up(lmid_bytes) : nullptr;
+  float* bandmax = sl.bandmax.bytes ? (float*)(base + sl.bandmax.off) : nullptr;
+  int* amb = (int*)(base + sl.amb.off);
+  float* bm1 = skip2 ? (float*)(base + sl.bm1.off) : nullptr;
+  unsigned char* live_mid = skip2 ? (unsigned char*)(base + sl.live_mid.off) : nullptr;
+  unsigned char* need = skip2 ? (unsigned char*)(base + sl.need.off) : nullptr;
   bool bm_done = false;
 
   // (amb[0]: the filter's list count; need: zeroed here for stage2_need_kernel; the peak mask
   // too when the blur runs over a live list, which writes the live tiles' words only)
-  const long long need16 = (long long)(up(need_bytes) / 16);
-  const long long mask16 = live_bytes ? (long long)(up(mask_bytes) / 16) : 0;
+  const long long need16 = (long long)(sl.need.padded() / 16);
+  const long long mask16 = sl.live.bytes ? (long long)(sl.mask.padded() / 16) : 0;
   hipLaunchKernelGGL(init_records_kernel,
                      dim3(std::max<long long>((n + 255) / 256, std::min<long long>((need16 + mask16 + 1023) / 1024, 2048))),
-                     dim3(256), 0, s, (char*)d_result, lay, n, nlimbs, live_bytes ? live_count : nullptr, amb,
+                     dim3(256), 0, s, (char*)d_result, lay, n, nlimbs, sl.live.bytes ? live_count : nullptr, amb,
                      (uint4*)need, need16, (uint4*)mask, mask16);
   PHIP(hipGetLastError());
 
@@ -3565,13 +3383,13 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
   }
   // blur + NMS (body.py:86-100)
   dim3 gb((W + NMS_TX - 1) / NMS_TX, (H + NMS_TY - 1) / NMS_TY, n * nparts);
-  tile_prof_arm((size_t)gb.x * gb.y * gb.z, s);
+  tile_prof_arm((size_t)gb.x * gb.y * gb.z, s, sw);
   const int tx = (int)gb.x, tyl = (int)gb.y;
   if (!multi && !fused && bm_done != (bool)plan.final_rs[0].bm)
     return post_fail(ISL_E_STATE, "body post: the final resize did not follow the plan");
   if (plan.blur == ISL_BLUR_MULTI_F64) {
     if ((rc = launch_blur<double, false>(gb, s, (const double*)heat, H, W, words, mask, thre1, 0, MapSrc{}, 0, nullptr,
-                                         nullptr, tx, tyl, nullptr, amb, true)))
+                                         nullptr, tx, tyl, nullptr, amb, plan.env_blur_exact, true)))
       return rc;
   } else if (plan.blur == ISL_BLUR_FUSED_LIVE) {
     // live-tile list (low-res bound), then the fused blur over live tiles only
@@ -3585,7 +3403,7 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
       PHIP(hipGetLastError());
       if ((rc = launch_blur<float, true, NMS_WSRC_ROWS, NMS_WSRC_COLS>(
                dim3(std::min((n_tiles + 7) / 8 * 8, 256 * 4)), s, (const float*)nullptr, H, W, words, mask, thre1, 0, fused_src, nparts,
-               live, live_count, tx, tyl, nullptr, amb, true)))
+               live, live_count, tx, tyl, nullptr, amb, plan.env_blur_exact, true)))
         return rc;
 #endif
     } else {
@@ -3593,7 +3411,7 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
                          tx, tyl, n_tiles, thre1, live, live_count);
       PHIP(hipGetLastError());
       if ((rc = launch_blur<float, true>(dim3(std::min((n_tiles + 7) / 8 * 8, 256 * 8)), s, (const float*)nullptr, H, W, words, mask,
-                                         thre1, 0, fused_src, nparts, live, live_count, tx, tyl, nullptr, amb, true)))
+                                         thre1, 0, fused_src, nparts, live, live_count, tx, tyl, nullptr, amb, plan.env_blur_exact, true)))
         return rc;
     }
   } else if (plan.blur == ISL_BLUR_BAND_LIVE) {
@@ -3604,11 +3422,11 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
                        words, tx, tyl, n_tiles, thre1, live, live_count, (const unsigned char*)live_mid);
     PHIP(hipGetLastError());
     if ((rc = launch_blur<float, false>(dim3(std::min((n_tiles + 7) / 8 * 8, 256 * 8)), s, (const float*)heat, H, W, words, mask,
-                                        thre1, 0, MapSrc{}, 0, live, live_count, tx, tyl, nullptr, amb, true)))
+                                        thre1, 0, MapSrc{}, 0, live, live_count, tx, tyl, nullptr, amb, plan.env_blur_exact, true)))
       return rc;
   } else if ((rc = launch_blur<float, false>(gb, s, (const float*)heat, H, W, words, mask, thre1, 0, MapSrc{}, 0, nullptr,
                                              nullptr, tx, tyl, plan.blur_bandmax ? (const float*)bandmax : nullptr, amb,
-                                             true))) {
+                                             plan.env_blur_exact, true))) {
     return rc;
   }
   PHIP(hipGetLastError());
@@ -3635,10 +3453,7 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
   ga.pair_keep = (int*)(pairs + slots * caps->max_pairs * 8);
   ga.order = ga.pair_keep + slots * caps->max_pairs;
   ga.used = used;
-  {   // ISLPOSE_LIMB_LDS=0: large pair sets on the per-thread pair loop (A/B and tests; read per call)
-    const char* e = getenv("ISLPOSE_LIMB_LDS");
-    ga.limb_lds = !(e && e[0] == '0');
-  }
+  ga.limb_lds = plan.env_limb_lds;   // 0: large pair sets on the per-thread pair loop
   ga.thre2 = po.thre2;
   ga.max_people = po.max_people;
   // the scoring over Z blocks per limb (MODE 1), then ranks and matches (MODE 2), or one block
@@ -3655,10 +3470,8 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
   // (the connection cache takes what is left of 64 KB of dynamic LDS, up to ASM_CONN_CACHE)
   const size_t sub_lds = asm_lds ? (size_t)caps->max_rows * (njoint + 1) * 8 : 0;
   const int conn_cap = (int)std::min<size_t>(ASM_CONN_CACHE, sub_lds < 65536 ? (65536 - sub_lds) / 40 : 0);
-  asm_prof_arm((size_t)n, s);
-  // ISLPOSE_ASM_REG=0: the table merge only (A/B; read per call)
-  const char* are = getenv("ISLPOSE_ASM_REG");
-  const int use_reg = !(are && are[0] == '0');
+  asm_prof_arm((size_t)n, s, sw);
+  const int use_reg = plan.env_asm_reg;   // 0: the table merge only
   if (kind == ISL_BODY25) {
     if (asm_lds)
       hipLaunchKernelGGL((assemble_kernel<true, ISL_BODY25>), dim3(n), dim3(64), sub_lds + (size_t)conn_cap * 40, s, ga,
@@ -3678,84 +3491,43 @@ extern "C" int isl_body_post_opts(isl_net* net, int n, int H, int W, int nscales
   return ISL_OK;
 }
 
-// scratch bytes of one hand post of n crops of h x w (layout: hand_post_launch)
-static size_t hand_post_bytes(int n, int h, int w, int nscales, const isl_scale_geom* geom) {
-  const int nparts = 21;
-  const size_t P = (size_t)h * w;
-  const int words = (w + 63) / 64;
-  size_t mid_bytes = 0;   // every scale's intermediate stays until the fused average
-  for (int si = 0; si < nscales; ++si)
-    if (!(geom[si].valid_h == h && geom[si].valid_w == w))
-      mid_bytes += (size_t)n * geom[si].valid_h * geom[si].valid_w * nparts * 4;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t avg_bytes = (size_t)n * nparts * P * 8, mask_bytes = (size_t)n * nparts * h * words * 8;
-  const size_t par_bytes = (size_t)n * nparts * P * 4, val_bytes = (size_t)n * nparts * P * 8;
-  const size_t st_bytes = (size_t)n * nparts * sizeof(CcStats);
-  const int cc_rows = std::max(1, CC_CHUNK / w), cc_chunks = (h + cc_rows - 1) / cc_rows;
-  const size_t ck_bytes = (size_t)n * nparts * cc_chunks * sizeof(CcChunk);
-  const size_t bs_bytes = (size_t)n * nparts * CC_KFAST * (P / 8192 + 1) * 8;
-  const size_t amb_bytes = ((size_t)((w + NMS_TX - 1) / NMS_TX) * ((h + NMS_TY - 1) / NMS_TY) * n * nparts + 1) * 4;
-  return up(avg_bytes) + up(mid_bytes) + up(mask_bytes) + up(par_bytes) + up(val_bytes) + up(st_bytes) + up(ck_bytes) +
-         up(bs_bytes) + up(amb_bytes);
-}
-
-// What hand_post_launch chooses on the host for crops of h x w (no device work): the launch
-// follows this plan, and isl_debug_hand_post_plan returns it.
-static void hand_post_plan(int h, int w, int nscales, const isl_scale_geom* geom, isl_hand_post_plan* p) {
-  memset(p, 0, sizeof(*p));
-  int ty = RA_TY;
-  for (int si = 0; si < nscales; ++si) {
-    const isl_scale_geom& g = geom[si];
-    const bool two_stage = !(g.valid_h == h && g.valid_w == w);
-    p->two_stage[si] = two_stage;
-    p->identity[si] = 0;   // both the x8 and the stage-2 source are interpolated
-    if (two_stage) p->stage1[si] = resize_form(1.0 / 8.0, false, g.valid_w, 1, false);
-    // rows per tile: every scale's source window fits the LDS rows
-    ty = fit_rows(ty, two_stage ? 1.0 / ((double)h / g.valid_h) : 1.0 / 8.0, p->identity[si]);
-  }
-  p->acc_ty = ty;
-  p->cc_lds = (long long)h * w <= CC_LDS_MAX;
-  p->cc_rows = std::max(1, CC_CHUNK / w);
-  p->cc_chunks = (h + p->cc_rows - 1) / p->cc_rows;
-}
-
 extern "C" int isl_debug_hand_post_plan(int h, int w, int nscales, const isl_scale_geom* geom,
                                         isl_hand_post_plan* out) {
   if (h <= 0 || w <= 0 || !out || !plan_geom_ok(nscales, geom))
     return post_fail(ISL_E_ARG, "isl_debug_hand_post_plan: bad argument");
-  hand_post_plan(h, w, nscales, geom, out);
+  hand_post_plan(h, w, nscales, geom, post_switches(), out);
   return ISL_OK;
 }
 
-// the kernels of one hand post (hand.py:51-74) on stream s, scratch at base
-// (hand_post_bytes); heat planes of scale si at d_heat[si] (NULL: the arena output)
+// plan and scratch layout of one hand post of n crops of h x w: what the entries allocate by
+// and hand_post_launch carves by
+static HandPostLayout hand_layout(int n, int h, int w, int nscales, const isl_scale_geom* geom,
+                                  const PostSwitches& sw, isl_hand_post_plan* plan) {
+  hand_post_plan(h, w, nscales, geom, sw, plan);
+  return hand_post_layout(*plan, n, h, w, nscales, geom);
+}
+
+// the kernels of one hand post (hand.py:51-74) on stream s, scratch at base (hand_layout's
+// total bytes); heat planes of scale si at d_heat[si] (NULL: the arena output)
 static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, const isl_scale_geom* geom,
                             const float* const* d_heat, int64_t* d_peaks, hipStream_t s, char* base, double thre,
-                            const float* const* mid_pre = nullptr, const uint8_t* flip = nullptr,
-                            double* d_scores = nullptr) {
+                            const PostSwitches& sw, const float* const* mid_pre = nullptr,
+                            const uint8_t* flip = nullptr, double* d_scores = nullptr) {
   const int nparts = 21, nch = 22;
   const size_t P = (size_t)h * w;
   const int words = (w + 63) / 64;
-  size_t mid_bytes = 0;   // every scale's intermediate stays until the fused average
-  for (int si = 0; si < nscales; ++si)
-    if (!(geom[si].valid_h == h && geom[si].valid_w == w))
-      mid_bytes += (size_t)n * geom[si].valid_h * geom[si].valid_w * nparts * 4;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t avg_bytes = (size_t)n * nparts * P * 8, mask_bytes = (size_t)n * nparts * h * words * 8;
-  const size_t par_bytes = (size_t)n * nparts * P * 4, val_bytes = (size_t)n * nparts * P * 8;
-  const size_t st_bytes = (size_t)n * nparts * sizeof(CcStats);
   isl_hand_post_plan plan;   // the resize forms, the rows per tile and the component path
-  hand_post_plan(h, w, nscales, geom, &plan);
+  const HandPostLayout sl = hand_layout(n, h, w, nscales, geom, sw, &plan);
   const int cc_rows = plan.cc_rows, cc_chunks = plan.cc_chunks;
-  double* avg = (double*)base;
-  float* mid = (float*)(base + up(avg_bytes));
-  unsigned long long* mask = (unsigned long long*)((char*)mid + up(mid_bytes));
-  int* parent = (int*)((char*)mask + up(mask_bytes));
-  double* vals = (double*)((char*)parent + up(par_bytes));
-  CcStats* stats = (CcStats*)((char*)vals + up(val_bytes));
-  CcChunk* cks = (CcChunk*)((char*)stats + up(st_bytes));
-  double* bsum = (double*)((char*)cks + up((size_t)n * nparts * cc_chunks * sizeof(CcChunk)));
-  int* amb = (int*)((char*)bsum + up((size_t)n * nparts * CC_KFAST * (P / 8192 + 1) * 8));
+  double* avg = (double*)(base + sl.avg.off);
+  float* mid = (float*)(base + sl.mid.off);   // every scale's intermediate stays until the fused average
+  unsigned long long* mask = (unsigned long long*)(base + sl.mask.off);
+  int* parent = (int*)(base + sl.parent.off);
+  double* vals = (double*)(base + sl.vals.off);
+  CcStats* stats = (CcStats*)(base + sl.stats.off);
+  CcChunk* cks = (CcChunk*)(base + sl.chunks.off);
+  double* bsum = (double*)(base + sl.bsum.off);
+  int* amb = (int*)(base + sl.amb.off);
   const float div_f = (float)nscales;
   MapSrcN fin;                        // per scale: the resize that lands on the crop
   float* midp = mid;
@@ -3793,9 +3565,9 @@ static int hand_post_launch(isl_net* net, int n, int h, int w, int nscales, cons
     PHIP(hipGetLastError());
   }
   dim3 gb((w + NMS_TX - 1) / NMS_TX, (h + NMS_TY - 1) / NMS_TY, n * nparts);
-  tile_prof_arm((size_t)gb.x * gb.y * gb.z, s);
+  tile_prof_arm((size_t)gb.x * gb.y * gb.z, s, sw);
   if (int rc = launch_blur<double, false>(gb, s, (const double*)avg, h, w, words, mask, thre, 1, MapSrc{}, 0, nullptr,
-                                          nullptr, (int)gb.x, (int)gb.y, nullptr, amb))
+                                          nullptr, (int)gb.x, (int)gb.y, nullptr, amb, sw.blur_exact))
     return rc;
   // the last kernel, in groups of CC_FLIP_CROPS crops whose mirror flags ride in the launch
   auto flips_of = [&](int c0, int nc) {
@@ -3865,9 +3637,11 @@ extern "C" int isl_hand_post_ex(isl_net* net, int n, int h, int w, int nscales, 
   isl_post_opts po;
   if (int orc = post_opts_resolve(opts, &po, "isl_hand_post_opts")) return orc;
   PHIP(hipSetDevice(net_device(net)));
-  char* base = (char*)net_scratch(net, hand_post_bytes(n, h, w, nscales, geom));
+  const PostSwitches sw = post_switches();   // read once per call
+  isl_hand_post_plan plan;
+  char* base = (char*)net_scratch(net, hand_layout(n, h, w, nscales, geom, sw, &plan).total);
   if (!base) return ISL_E_HIP;
-  return hand_post_launch(net, n, h, w, nscales, geom, d_heat, d_peaks, (hipStream_t)stream, base, po.hand_thre,
+  return hand_post_launch(net, n, h, w, nscales, geom, d_heat, d_peaks, (hipStream_t)stream, base, po.hand_thre, sw,
                           nullptr, flip, d_scores);
 }
 
@@ -3908,11 +3682,15 @@ extern "C" int isl_hand_post_crops_ex(isl_net* net, int n, const int32_t* crop_w
   PostLanes* L = net_post_lanes(net);
   if (!L) return ISL_E_HIP;
   const int nl = std::min(n, ISL_POST_LANES);
+  const PostSwitches sw = post_switches();   // read once per call
   // lane k takes crops k, k + nl, ...; size its scratch for the largest first, before any
   // launch of this call (a grown buffer is reallocated only once its lane has drained)
   for (int k = 0; k < nl; ++k) {
     size_t need = 0;
-    for (int i = k; i < n; i += nl) need = std::max(need, hand_post_bytes(1, crop_w[i], crop_w[i], nscales, geom + (size_t)i * nscales));
+    for (int i = k; i < n; i += nl) {
+      isl_hand_post_plan plan;
+      need = std::max(need, hand_layout(1, crop_w[i], crop_w[i], nscales, geom + (size_t)i * nscales, sw, &plan).total);
+    }
     if (need > L->bytes[k]) {
       PHIP(hipStreamSynchronize(L->stream[k]));
       if (L->scratch[k]) PHIP(hipFree(L->scratch[k]));
@@ -3964,7 +3742,7 @@ extern "C" int isl_hand_post_crops_ex(isl_net* net, int n, const int32_t* crop_w
         lh.dh = h8 * 8; lh.dw = w8 * 8; lh.scy = lh.scx = 1.0 / 8.0; lh.cn = 22; lh.identity = 0;
         mid_all[si] = (float*)(base + off[si] - 1);
         if ((rc = launch_resize(lh, n, 21, g.valid_h, g.valid_w, 1, 1.f, mid_all[si], s,
-                                resize_form(lh.scy, false, g.valid_w, 1, false))))
+                                resize_form(lh.scy, false, g.valid_w, 1, false, sw))))
           return rc;
       }
     }
@@ -3981,7 +3759,7 @@ extern "C" int isl_hand_post_crops_ex(isl_net* net, int n, const int32_t* crop_w
       mp[si] = mid_all[si] ? mid_all[si] + (size_t)i * 21 * g.valid_h * g.valid_w : nullptr;
     }
     const int rc = hand_post_launch(net, 1, crop_w[i], crop_w[i], nscales, geom + (size_t)i * nscales, hp,
-                                    d_peaks + (size_t)i * 42, L->stream[k], (char*)L->scratch[k], po.hand_thre, mp,
+                                    d_peaks + (size_t)i * 42, L->stream[k], (char*)L->scratch[k], po.hand_thre, sw, mp,
                                     flip ? flip + i : nullptr, d_scores ? d_scores + (size_t)i * 21 : nullptr);
     if (rc) return rc;
   }

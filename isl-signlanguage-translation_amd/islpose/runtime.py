@@ -292,7 +292,8 @@ class IslBodyPostPlan(ctypes.Structure):
                   "stage2_ty", "limb_z", "env_fused_blur", "env_fused_wide", "env_blur_list", "env_blur_bands",
                   "env_resize_skip", "env_resize_v4", "env_blur_exact")] +
                 [("scale_two_stage", ctypes.c_int32 * PLAN_SCALES), ("stage1", IslResizePlan * PLAN_SCALES),
-                 ("final_rs", IslResizePlan * PLAN_SCALES), ("reserved", ctypes.c_int32 * 6)])
+                 ("final_rs", IslResizePlan * PLAN_SCALES), ("env_limb_lds", ctypes.c_int32),
+                 ("env_asm_reg", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)])
 
 
 class IslHandPostPlan(ctypes.Structure):

@@ -28,7 +28,8 @@ def test_symbols_declared_and_exported():
     assert re.search(r"#define\s+ISL_PLAN_SCALES\s+%d\b" % rt.PLAN_SCALES, text)
     for i, name in enumerate(rt.BLUR_BRANCHES):
         assert re.search(r"ISL_BLUR_%s\s*=\s*%d\b" % (name, i), text)
-    # the ctypes mirrors: 18 scalars + 8 flags + 2 x 8 resize plans of 6 ints + 6 reserved; 2 x 8 + 8 x 6 + 4 + 4
+    # the ctypes mirrors: 18 scalars + 8 flags + 2 x 8 resize plans of 6 ints + 2 switches + 4 reserved
+    # (the two took reserved slots: the size stands); 2 x 8 + 8 x 6 + 4 + 4
     assert ctypes.sizeof(rt.IslResizePlan) == 24
     assert ctypes.sizeof(rt.IslBodyPostPlan) == 4 * (18 + 8 + 6) + 2 * 8 * 24
     assert ctypes.sizeof(rt.IslHandPostPlan) == 4 * (16 + 4 + 4) + 8 * 24
