@@ -621,6 +621,55 @@ int isl_sign_grad(const float* d_params, int n_features, int window, int n_class
                   const uint64_t* d_ids, int batch, const isl_sign_train_opts* opts, float* d_loss,
                   float* d_grad, void* d_workspace, void* stream);
 
+/* Keypoint-space augmentation of the classifier's windows, in one launch (csrc/sign_augment.hip;
+ * DESIGN.md section 4.2m holds the definition).  Output window k, float32 [window][n_features], is
+ * item k's view of a resident row store d_rows [n_rows][n_features]:
+ *   rows      n_features = 2 * n_body + n_slots * 3 * n_hand: n_body x, n_body y, then per hand slot
+ *             n_hand x, n_hand y, n_hand labels.  A pair (x, y) is absent iff both values are 0.
+ *   frames    output frame t reads source row
+ *             r = floor(((2t - (window-1)) * q + 16 * (window-1) + 16) / 32) + start of the item's
+ *             source d_rows[row0 .. row0 + nrows); r outside [0, nrows) gives an all-zero frame, and
+ *             so does a dropped frame: (sm(kw ^ (16 << 32 | t)) >> 40) < floor(drop * 2^24 + 0.5),
+ *             kw = sm(sm(seed ^ step) ^ id), sm the splitmix64 finaliser of isl_sign_grad.
+ *   pairs     of a live frame, in fp64 without fused multiply-adds: X = (m0*x + m1*y) + m2,
+ *             Y = (m3*x + m4*y) + m5; with jitter > 0, X += jitter * (u * 2^-23 - 1) with
+ *             u = sm(kw ^ (17 << 32 | (t * 512 + 2p))) >> 40, p the pair's index in the row, and Y
+ *             the same with index + 1; both rounded once to fp32; if both are then 0, x is stored as
+ *             2^-10 (a present point never turns absent).  Absent pairs are stored as (0, 0); labels
+ *             are copied.  Points are not clipped to any frame.
+ *   items     an item with nrows < 1, q outside [8, 32], row0 < 0 or row0 + nrows > n_rows gives an
+ *             all-zero window; no row outside the store is addressed.
+ * A window depends only on its item, the rows it names and (seed, step, drop, jitter).  d_windows
+ * must not overlap d_rows.  Plain loads and stores, no host synchronisation.
+ * ISL_E_ARG, before any device work, for: n_items < 0 or > 65535, and with n_items > 0 a NULL
+ * pointer, n_rows < 0, window outside [1, 32], n_features outside [1, 256], a negative layout count,
+ * a layout whose size is not n_features, drop not a number in [0, 0.9], jitter not finite and >= 0,
+ * a reserved field not zero.  n_items == 0 returns at once. */
+typedef struct {
+  int64_t row0;      /* first row of the source (a clip, or a pre-cut window) in d_rows */
+  int32_t nrows;     /* rows of the source, >= 1 */
+  int32_t start;     /* source row of output frame 0 at speed 1; may be negative */
+  int32_t q;         /* speed in 1/16: 16 = as recorded; in [8, 32] */
+  int32_t reserved;  /* 0 */
+  uint64_t id;       /* sample id of the draws made in the kernel */
+  double m[6];       /* x' = (m0*x + m1*y) + m2;  y' = (m3*x + m4*y) + m5 */
+} isl_sign_aug_item; /* 80 bytes */
+
+typedef struct {
+  int32_t n_body, n_slots, n_hand, reserved;
+} isl_sign_aug_layout;
+
+typedef struct {
+  float drop, jitter;
+  uint64_t seed, step;
+  int32_t reserved[4];
+} isl_sign_aug_opts;
+
+int isl_sign_aug_opts_default(isl_sign_aug_opts* opts);   /* 0, 0, seed 0, step 0 */
+int isl_sign_augment(const float* d_rows, int64_t n_rows, int n_features, const isl_sign_aug_layout* layout,
+                     const isl_sign_aug_item* d_items, int n_items, int window,
+                     const isl_sign_aug_opts* opts, float* d_windows, void* stream);
+
 /* ---- augmented copies of resident frames --------------------------------- */
 
 /* One variant of a uint8 [H,W,3] frame, the reference's dataset augmentation

@@ -3,6 +3,9 @@ def __getattr__(name):
     if name == "SignTrainer":
         from .train import SignTrainer
         return SignTrainer
+    if name == "WindowAugment":
+        from .sign_augment import WindowAugment
+        return WindowAugment
     if name == "SignClassifier":
         from .translate import SignClassifier
         return SignClassifier

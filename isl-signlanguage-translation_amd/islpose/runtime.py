@@ -127,6 +127,7 @@ EXPORTS = ["isl_abi_version", "isl_last_error", "isl_net_create", "isl_net_destr
            "isl_body_post_opts", "isl_hand_post_opts", "isl_hand_post_crops_opts",
            "isl_net_preprocess_crops_flip", "isl_hand_post_ex", "isl_hand_post_crops_ex", "isl_augment",
            "isl_draw", "isl_sign_train_opts_default", "isl_sign_grad_workspace", "isl_sign_grad",
+           "isl_sign_aug_opts_default", "isl_sign_augment",
            "isl_debug_conv3x3", "isl_debug_conv", "isl_debug_body_post_plan", "isl_debug_hand_post_plan"]
 
 
@@ -174,6 +175,26 @@ class IslSignTrainOpts(ctypes.Structure):
     """isl_sign_train_opts: the rates of the three Dropout layers and of the recurrent dropout, each
     in [0, 0.9] (0: off); seed and step of the counter-based draws; reserved zero."""
     _fields_ = [("p_drop", ctypes.c_float), ("p_rec", ctypes.c_float), ("seed", ctypes.c_uint64),
+                ("step", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 4)]
+
+
+class IslSignAugItem(ctypes.Structure):
+    """isl_sign_aug_item (80 bytes): the source rows [row0, row0 + nrows) of the store, the source
+    row `start` of output frame 0, the speed q in 1/16, the sample id of the kernel's draws, and the
+    affine map m of every present pair."""
+    _fields_ = [("row0", ctypes.c_int64), ("nrows", ctypes.c_int32), ("start", ctypes.c_int32),
+                ("q", ctypes.c_int32), ("reserved", ctypes.c_int32), ("id", ctypes.c_uint64),
+                ("m", ctypes.c_double * 6)]
+
+
+class IslSignAugLayout(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_body", "n_slots", "n_hand", "reserved")]
+
+
+class IslSignAugOpts(ctypes.Structure):
+    """isl_sign_aug_opts: frame-drop rate in [0, 0.9], jitter amplitude >= 0 (both 0: off); seed and
+    step of the counter-based draws; reserved zero."""
+    _fields_ = [("drop", ctypes.c_float), ("jitter", ctypes.c_float), ("seed", ctypes.c_uint64),
                 ("step", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 4)]
 
 
@@ -419,6 +440,9 @@ def lib():
     L.isl_sign_grad_workspace.argtypes = [i32, i32, i32, ctypes.POINTER(i64)]
     L.isl_sign_grad.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, ctypes.POINTER(IslSignTrainOpts), vp, vp,
                                 vp, vp]
+    L.isl_sign_aug_opts_default.argtypes = [ctypes.POINTER(IslSignAugOpts)]
+    L.isl_sign_augment.argtypes = [vp, i64, i32, ctypes.POINTER(IslSignAugLayout), vp, i32, i32,
+                                   ctypes.POINTER(IslSignAugOpts), vp, vp]
     L.isl_debug_conv3x3.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]
     L.isl_debug_conv.argtypes = [ctypes.POINTER(IslDebugConvDesc), vp, vp, vp, vp, vp, vp,
                                  ctypes.POINTER(IslDebugConvResult)]
@@ -478,6 +502,22 @@ def augment(src_u8, items, out=None, stream=None):
     with torch.cuda.device(src_u8.device):
         s = stream if stream is not None else torch.cuda.current_stream(src_u8.device)
         check(lib().isl_augment(ptr(src_u8), n, H, W, ptr(out), arr, m, ctypes.c_void_p(s.cuda_stream)), "isl_augment")
+    return out
+
+
+def sign_augment(rows_t, layout, items_t, n_items, window, opts, out, stream=None):
+    """isl_sign_augment as it is: rows_t cuda fp32 [n_rows, F] (contiguous), layout (n_body, n_slots,
+    n_hand), items_t a cuda uint8 tensor holding n_items isl_sign_aug_item records (not validated
+    here: islpose.sign_augment.WindowAugment.apply does that), opts an IslSignAugOpts, out cuda fp32
+    with n_items * window * F elements; one launch on `stream` (None: the current stream of the
+    rows' device).  Returns out."""
+    import torch
+    lay = IslSignAugLayout(int(layout[0]), int(layout[1]), int(layout[2]), 0)
+    with torch.cuda.device(rows_t.device):
+        s = stream if stream is not None else torch.cuda.current_stream(rows_t.device)
+        check(lib().isl_sign_augment(ptr(rows_t), rows_t.shape[0], rows_t.shape[1], ctypes.byref(lay), ptr(items_t),
+                                     n_items, window, ctypes.byref(opts), ptr(out), ctypes.c_void_p(s.cuda_stream)),
+              "isl_sign_augment")
     return out
 
 

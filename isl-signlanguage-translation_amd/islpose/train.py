@@ -6,7 +6,9 @@ sparse categorical cross-entropy and the backward pass through time are one HIP 
 supplies the optimizer and the tensors.  DESIGN.md section 4.2k holds the definition.  Two
 deliberate deviations from ``keras.Model.fit``: the batch normalisations use their stored moving
 statistics (BN0's are set from the data by ``calibrate_bn0``), and recurrent dropout draws one mask
-per direction and window.
+per direction and window.  ``step`` / ``fit`` / ``fit_clips`` take ``augment=``, a
+``sign_augment.WindowAugment`` that redraws every batch in keypoint space by one more launch
+(DESIGN.md section 4.2m).
 
 Without libislpose.so or a GPU this raises like the rest of the product layer: no CPU fallback.
 """
@@ -153,8 +155,29 @@ class SignTrainer:
                                       ptr(grad), ptr(ws), stream_handle()), "isl_sign_grad")
         return loss, grad
 
-    def step(self, windows, labels, weights=None, ids=None):
-        """One optimizer step on a batch; returns l_b [B] (with this step's dropout masks)."""
+    def _augmented(self, augment, rows, idx, window, nrows, row0, base=0):
+        """The batch `idx` (numpy dataset indices, the dropout's ids) as windows built by `augment`
+        from the resident rows [n_rows, F]: items of this trainer's seed and step_count."""
+        items = augment.items(idx, self.step_count, nrows, row0, base, seed=self.seed)
+        return augment.apply(rows, items, window, self.step_count, seed=self.seed)
+
+    def step(self, windows, labels, weights=None, ids=None, augment=None):
+        """One optimizer step on a batch; returns l_b [B] (with this step's dropout masks).
+        augment: a sign_augment.WindowAugment; the batch is then its view of `windows` (window b is
+        the source of item b, drawn with the dropout's ids, this trainer's seed and step_count)."""
+        if augment is not None:
+            import torch
+            x = windows if isinstance(windows, torch.Tensor) else torch.from_numpy(np.asarray(windows, np.float32))
+            check_windows_shape(tuple(x.shape), self.n_features)
+            x = x.to(self.device, torch.float32).contiguous()
+            B, T, F = x.shape
+            if ids is None:
+                idx = np.arange(B, dtype=np.uint64)
+            else:
+                idx = np.asarray(ids.cpu() if hasattr(ids, "cpu") else ids).astype(np.uint64)
+            if idx.shape != (B,):
+                raise ValueError("ids must be [%d], got %s" % (B, idx.shape))
+            windows = self._augmented(augment, x.view(B * T, F), idx, T, T, np.arange(B, dtype=np.int64) * T)
         loss, grad = self.loss_and_grad(windows, labels, weights, ids, train=True)
         self.params.grad = grad
         self.optimizer.step()
@@ -188,28 +211,78 @@ class SignTrainer:
             n += int(keep.sum())
         return (nll / n, hit / n) if n else (0.0, 0.0)
 
-    def fit(self, windows, labels, epochs, batch=256, val=None, shuffle_seed=0):
+    def fit(self, windows, labels, epochs, batch=256, val=None, shuffle_seed=0, augment=None):
         """`epochs` passes over [N, T, F] windows in batches of `batch`, reshuffled per epoch from
-        shuffle_seed; the dropout ids are the dataset indices.  val: (windows, labels) or None.
-        Returns one dict per epoch: epoch, loss (mean l_b over the epoch's steps), and with val
-        val_loss and val_acc."""
+        shuffle_seed; the dropout ids are the dataset indices.  val: (windows, labels) or None
+        (never augmented).  augment: a sign_augment.WindowAugment; every batch is then built by its
+        one launch from the resident windows (window i is the source of item i: row0 = i * T,
+        nrows = T), redrawn every step.  Returns one dict per epoch: epoch, loss (mean l_b over the
+        epoch's steps), and with val val_loss and val_acc."""
         x = np.asarray(windows, np.float32)
         check_windows_shape(x.shape, self.n_features)
         lab = check_labels(labels, len(x), self.n_classes)
+        import torch
+        xd = torch.from_numpy(x).to(self.device)
+        if augment is None:
+            def batch_of(order, idx):
+                return xd[idx]
+        else:
+            T = x.shape[1]
+            rows = xd.view(len(x) * T, x.shape[2])
+
+            def batch_of(order, idx):
+                return self._augmented(augment, rows, order, T, T, order.astype(np.int64) * T)
+        return self._run(batch_of, len(x), lab, epochs, batch, val, shuffle_seed)
+
+    def fit_clips(self, clips, labels, epochs, batch=256, val=None, shuffle_seed=0, augment=None, window=20,
+                  stride=5):
+        """`fit` on clips instead of pre-cut windows: clips is a sequence of [n_k, F] row arrays,
+        labels one label per clip.  The rows are resident once, as one store; there is one item per
+        (clip, static position), enumerated as tools/train_sign.py's cut_windows cuts them (a window
+        every `stride` rows while a full one fits, one window for a shorter clip), and every batch
+        is built from the store by one isl_sign_augment launch.  A temporal shift or a speed change
+        therefore reads the clip's real neighbouring frames.  augment None: identity items, which
+        give the bits of `fit` on the cut windows."""
+        from . import sign_augment as sa
+        T = sa.check_window(window)
+        if isinstance(stride, bool) or int(stride) != stride or int(stride) < 1:
+            raise ValueError("stride must be an integer >= 1, got %r" % (stride,))
+        cl = [np.asarray(c, np.float32) for c in clips]
+        for c in cl:
+            if c.ndim != 2 or c.shape[1] != self.n_features:
+                raise ValueError("a clip must be [n, %d] rows, got %s" % (self.n_features, c.shape))
+        clip_lab = check_labels(labels, len(cl), self.n_classes)
+        if augment is None:
+            augment = sa.WindowAugment(layout=sa.identity_layout(self.n_features))
+        lengths = np.array([len(c) for c in cl], np.int64)
+        which, base = sa.clip_items(lengths, T, int(stride))
+        first = np.concatenate([[0], np.cumsum(lengths)])[:-1] if len(cl) else np.zeros(0, np.int64)
+        row0, nrows = first[which], lengths[which]
+        import torch
+        store = np.concatenate(cl) if len(which) else np.zeros((1, self.n_features), np.float32)
+        rows = torch.from_numpy(np.ascontiguousarray(store)).to(self.device)
+
+        def batch_of(order, idx):
+            return self._augmented(augment, rows, order, T, nrows[order], row0[order], base[order])
+        return self._run(batch_of, len(which), clip_lab[which], epochs, batch, val, shuffle_seed)
+
+    def _run(self, batch_of, n, lab, epochs, batch, val, shuffle_seed):
+        """The loop of fit and fit_clips over n samples: batch_of(order, idx) gives the windows of
+        the dataset indices `order` (numpy; `idx` the same on the device)."""
         if int(epochs) < 0 or int(batch) < 1:
             raise ValueError("epochs must be >= 0 and batch >= 1")
         import torch
-        xd = torch.from_numpy(x).to(self.device)
         ld = torch.from_numpy(lab).to(self.device)
         rng = np.random.RandomState(shuffle_seed)
         history = []
         for ep in range(int(epochs)):
-            order = rng.permutation(len(x))
+            order = rng.permutation(n)
             total = torch.zeros((), dtype=torch.float64, device=self.device)
             for s in range(0, len(order), int(batch)):
-                idx = torch.from_numpy(order[s:s + int(batch)]).to(self.device)
-                total += self.step(xd[idx], ld[idx], ids=idx).sum(dtype=torch.float64)
-            row = {"epoch": ep, "loss": float(total) / max(1, len(x))}
+                part = order[s:s + int(batch)]
+                idx = torch.from_numpy(part).to(self.device)
+                total += self.step(batch_of(part, idx), ld[idx], ids=idx).sum(dtype=torch.float64)
+            row = {"epoch": ep, "loss": float(total) / max(1, n)}
             if val is not None:
                 row["val_loss"], row["val_acc"] = self.evaluate(val[0], val[1], int(batch))
             history.append(row)

@@ -494,6 +494,13 @@ def train(args):
     clf = tr.classifier()
     runs = {"hip_step": lambda: tr.step(x, y32), "torch_step": lambda: torch_train_step(tw, topt, x, y, 0.2, 0.2),
             "classify": lambda: clf(x)}
+    if args.augment:                                  # --augment SPEC: the step with its batch built by isl_sign_augment
+        from islpose.sign_augment import WindowAugment
+        aug = WindowAugment.parse(args.augment, seed=args.augment_seed)
+        rows, ids = x.view(B * T, F), np.arange(B, dtype=np.uint64)
+        row0 = np.arange(B, dtype=np.int64) * T
+        runs["hip_step_aug"] = lambda: tr.step(x, y32, augment=aug)
+        runs["augment_only"] = lambda: aug.apply(rows, aug.items(ids, tr.step_count, T, row0), T, tr.step_count)
     warm, steps, rounds = 10, 30, 3
     for fn in runs.values():
         for _ in range(warm):
@@ -516,7 +523,9 @@ def train(args):
         res[k + "_us"] = [round(t * 1e3, 1) for t in v]
         res[k + "_windows_per_s"] = round(B / (float(np.median(v)) * 1e-3), 1)
     res["torch_over_hip"] = round(float(np.median(ms["torch_step"]) / np.median(ms["hip_step"])), 2)
-    out = os.path.join(REPO, "profiles", "signtrain")
+    if args.augment:
+        res["augment"] = args.augment
+    out = os.path.join(REPO, "profiles", "signaug" if args.augment else "signtrain")
     os.makedirs(out, exist_ok=True)
     with open(os.path.join(out, "train.jsonl"), "a") as f:
         f.write(json.dumps(res) + "\n")
@@ -556,7 +565,9 @@ def main():
                          "crop of a frame)")
     ap.add_argument("--augment", default=None,
                     help="C5: augmented variants per frame, e.g. rotation:30,solarize:192 (RandomRotation / "
-                         "RandomSolarize, islpose.augment.parse_spec); default: none")
+                         "RandomSolarize, islpose.augment.parse_spec); TRAIN: also time the step with its batch "
+                         "augmented in keypoint space, e.g. rot:15,scale:0.1,tshift:3,drop:0.1 "
+                         "(islpose.sign_augment.WindowAugment.parse); default: none")
     ap.add_argument("--augment-seed", type=int, default=0, help="C5: seed of the --augment draws")
     ap.add_argument("--write-jpg", action="store_true",
                     help="C5: also write every frame's stick-model JPEG (KeypointExtractor write_jpg)")

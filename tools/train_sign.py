@@ -13,6 +13,12 @@ stem, so a video's augmented variants never straddle the split.  Then: BN0 stati
 training windows, SignTrainer.fit, one JSON line per epoch, and <out> as
 np.savez(path, *weights), which SignClassifier(path) loads.
 
+--augment SPEC redraws every training window at every step in keypoint space (islpose.sign_augment,
+DESIGN.md section 4.2m), e.g. --augment rot:15,scale:0.1,shift:0.05,speed:0.2,tshift:3,drop:0.1,jitter:2;
+--frame W,H is the size of the videos' frames.  With --clips the rows stay whole per clip
+(SignTrainer.fit_clips), so a temporal shift or a speed change reads the clip's real neighbouring
+frames instead of the zero padding of a pre-cut window.  Validation is never augmented.
+
 The parsing and windowing functions import without a GPU.
 """
 from __future__ import annotations
@@ -104,14 +110,17 @@ def split_stems(clips, val_share: float, seed: int):
 
 
 def build_dataset(base: str, classes_file=None, stride: int = 5, val_share: float = 0.2, seed: int = 0,
-                  window: int = WINDOW):
+                  window: int = WINDOW, keep_rows: bool = False):
     """The tree -> dict(names, train=(windows, labels), val=(windows, labels), clips): fp32 windows
-    [n, window, 156], int32 labels.  A clip whose expression is not in the class list is an error."""
+    [n, window, 156], int32 labels.  A clip whose expression is not in the class list is an error.
+    keep_rows: also train_rows = (the fp32 [n_k, 156] rows of every training clip, one label per
+    clip), in the order the training windows were cut from them."""
     clips = scan_tree(base)
     names = class_names(clips, classes_file)
     index = {n: i for i, n in enumerate(names)}
     val_videos = split_stems(clips, val_share, seed)
     parts = {"train": ([], []), "val": ([], [])}
+    train_rows = ([], [])
     for c in clips:
         if c["expression"] not in index:
             raise ValueError("expression %r is not in the class list" % c["expression"])
@@ -119,14 +128,21 @@ def build_dataset(base: str, classes_file=None, stride: int = 5, val_share: floa
         for p in c["frames"]:
             with open(p) as f:
                 rows.append(frame_row(f.read()))
-        w = cut_windows(np.array(rows).reshape(len(rows), N_FEATURES), window, stride).astype(np.float32)
-        part = parts["val" if (c["type"], c["expression"], c["stem"]) in val_videos else "train"]
+        rows = np.array(rows).reshape(len(rows), N_FEATURES)
+        w = cut_windows(rows, window, stride).astype(np.float32)
+        in_val = (c["type"], c["expression"], c["stem"]) in val_videos
+        part = parts["val" if in_val else "train"]
+        if keep_rows and not in_val:
+            train_rows[0].append(rows.astype(np.float32))
+            train_rows[1].append(index[c["expression"]])
         part[0].append(w)
         part[1].append(np.full(len(w), index[c["expression"]], np.int32))
     out = {"names": names, "clips": clips}
     for k, (ws, ls) in parts.items():
         out[k] = (np.concatenate(ws) if ws else np.zeros((0, window, N_FEATURES), np.float32),
                   np.concatenate(ls) if ls else np.zeros(0, np.int32))
+    if keep_rows:
+        out["train_rows"] = (train_rows[0], np.array(train_rows[1], np.int32))
     return out
 
 
@@ -144,15 +160,29 @@ def main():
     ap.add_argument("--p-rec", type=float, default=0.2)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--weights", help="start from these weights (.npz) instead of keras' initialisers")
+    ap.add_argument("--augment", default=None,
+                    help="keypoint-space augmentation of every training window at every step, e.g. "
+                         "rot:15,scale:0.1,shift:0.05,speed:0.2,tshift:3,drop:0.1,jitter:2 "
+                         "(islpose.sign_augment.WindowAugment.parse); default: none")
+    ap.add_argument("--frame", default="1920,1080", help="--augment: W,H of the videos' frames")
+    ap.add_argument("--clips", action="store_true",
+                    help="keep the rows per clip and cut the windows on the GPU (SignTrainer.fit_clips)")
     a = ap.parse_args()
 
-    data = build_dataset(a.features, a.classes, a.stride, a.val_share, a.seed)
+    from islpose.sign_augment import WindowAugment
+    augment = WindowAugment.parse(a.augment, frame=tuple(float(v) for v in a.frame.split(",")))
+    data = build_dataset(a.features, a.classes, a.stride, a.val_share, a.seed, keep_rows=a.clips)
     from islpose.train import SignTrainer
     tr = SignTrainer(a.weights, N_FEATURES, len(data["names"]), a.p_drop, a.p_rec, a.seed, a.lr)
     tr.calibrate_bn0(data["train"][0])
     val = data["val"] if len(data["val"][0]) else None
     for ep in range(a.epochs):
-        row = tr.fit(data["train"][0], data["train"][1], 1, a.batch, val, shuffle_seed=a.seed + ep)[0]
+        if a.clips:
+            row = tr.fit_clips(data["train_rows"][0], data["train_rows"][1], 1, a.batch, val, shuffle_seed=a.seed + ep,
+                               augment=augment, window=WINDOW, stride=a.stride)[0]
+        else:
+            row = tr.fit(data["train"][0], data["train"][1], 1, a.batch, val, shuffle_seed=a.seed + ep,
+                         augment=augment)[0]
         row["epoch"] = ep
         print(json.dumps(row), flush=True)
     out = a.out if a.out.endswith(".npz") else a.out + ".npz"
