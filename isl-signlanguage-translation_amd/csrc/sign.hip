@@ -84,8 +84,7 @@ __global__ __launch_bounds__(SC_BLOCK) void sign_classify_kernel(SignArgs a) {
   __syncthreads();
   float mx = -INFINITY;
   for (int c = tid; hw && c < C; c += SC_THREADS) {
-    float acc = a.b3[c];
-    for (int i = 0; i < SC_D; ++i) acc += s_y2[i] * a.d3[i * C + c];
+    const float acc = sc_logit(s_y2, a.d3, a.b3, C, c);
     s_logit[c] = acc;
     mx = fmaxf(mx, acc);
   }

@@ -64,6 +64,15 @@ __device__ __forceinline__ float sc_bn(const float* p, int n, int j, float v) {
   return (v - p[2 * n + j]) / sqrtf(p[3 * n + j] + SC_EPS) * p[j] + p[n + j];
 }
 
+// Logit of class c: the 32 products summed in order, then the bias.  The bias goes last: a sum
+// that starts at b3[c] rounds every partial at the bias's magnitude, and a large bias (a softmax is
+// blind to a shift common to all classes) then costs its ulp 32 times instead of once.
+__device__ __forceinline__ float sc_logit(const float* y2, const float* d3, const float* b3, int C, int c) {
+  float acc = 0.0f;
+  for (int i = 0; i < SC_D; ++i) acc += y2[i] * d3[i * C + c];
+  return acc + b3[c];
+}
+
 // z[t][d][g] = b[g] + sum_f in[t][f] * K[f][g] (one lane per (d, g, range of 8 steps)).
 // A lone window is latency-bound: 1024 lanes on one CU, four K rows per iteration and
 // 16-byte LDS reads of the inputs; the sum over f keeps its order.

@@ -263,8 +263,7 @@ __global__ __launch_bounds__(SC_BLOCK) void sign_grad_kernel(SignTrainArgs a) {
     __syncthreads();
     float mx = -INFINITY;
     for (int c = tid; hw && c < C; c += SC_THREADS) {
-      float acc = w.b3[c];
-      for (int i = 0; i < SC_D; ++i) acc += s_y2[i] * w.d3[i * C + c];
+      const float acc = sc_logit(s_y2, w.d3, w.b3, C, c);
       s_logit[c] = acc;
       mx = fmaxf(mx, acc);
     }

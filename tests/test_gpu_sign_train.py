@@ -12,6 +12,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import _sign_ref as dense
 import _sign_train_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +27,9 @@ SHAPES = [(1, 12, 7, 2),        # a single step
           (20, 156, 167, 6),    # the workload's own shape
           (32, 256, 1024, 3),   # every limit at once: the LDS budget
           (20, 156, 2, 1),      # batch 1, two classes
-          (3, 8, 3, 300)]       # workgroups that own two windows: the accumulation and the 256-slice reduce
+          (3, 8, 3, 300),       # workgroups that own two windows: the accumulation and the 256-slice reduce
+          (9, 12, 7, 4)]        # DENSE: the classifier tests' weights and windows (tests/_sign_ref.py)
+DENSE = (9, 12, 7, 4)           # no constant bias block, b3 != 0, signed features, a -0.0 frame, two step ranges
 DROPOUT_CASES = [(0.2, 0.2, (5, 12, 7, 4)), (0.5, 0.5, (5, 12, 7, 4)),
                  (0.2, 0.2, (20, 156, 167, 3)), (0.5, 0.5, (20, 156, 167, 3))]
 
@@ -39,6 +42,8 @@ def _case(T, F, C, B):
     if key not in _cache:
         w = ref.trained_like_weights(F, C, seed=T + 1)
         x = ref.windows_like(B, T, F, seed=T + C, masked=0.2)
+        if (T, F, C, B) == DENSE:
+            w, x = dense.dense_weights(F, C, seed=T + 1), dense.windows(B, T, F, seed=T + C)
         if (T, F) == (5, 10):
             x[:, :, 0] = np.maximum(x[:, :, 0], 1)      # every step unmasked, then:
             x[0, 0] = 0                                 # a leading,
@@ -214,19 +219,34 @@ def test_invariances():
     assert not torch.equal(g_w0, g1)
 
 
+def _loss_against_inference(w, x, F, C):
+    """|exp(-l_b) - p[label]| / p[label] per window, train=False, and l_b."""
+    from islpose.train import SignTrainer
+    B = len(x)
+    labels = np.random.RandomState(2).randint(0, C, B)
+    tr = SignTrainer(w, F, C)
+    loss, _ = tr.loss_and_grad(x, labels, train=False)
+    loss = loss.cpu().numpy().astype(np.float64)
+    p = tr.classifier()(x).cpu().numpy().astype(np.float64)[np.arange(B), labels]
+    return np.abs(np.exp(-loss) - p) / p, loss
+
+
 def test_loss_agrees_with_inference():
     """exp(-l_b) with train=False against isl_sign_classify's p[label], to 1e-6 relative."""
-    from islpose.train import SignTrainer
     T, F, C, B = 20, 156, 167, 37
     w = ref.trained_like_weights(F, C)
     x = ref.windows_like(B, T, F)
     x[5] = 0
-    labels = np.random.RandomState(2).randint(0, C, B)
-    tr = SignTrainer(w, F, C)
-    loss, _ = tr.loss_and_grad(x, labels, train=False)
-    p = tr.classifier()(x).cpu().numpy().astype(np.float64)[np.arange(B), labels]
-    rel = np.abs(np.exp(-loss.cpu().numpy().astype(np.float64)) - p) / p
+    rel, _ = _loss_against_inference(w, x, F, C)
     print("max rel %.3g" % rel.max())
+    assert rel.max() <= 1e-6
+
+
+def test_loss_agrees_with_inference_on_dense_weights():
+    """The same on the classifier tests' dense weights and signed windows (b3 != 0, l_b up to 14)."""
+    T, F, C, B = 20, 156, 167, 37
+    rel, loss = _loss_against_inference(dense.dense_weights(F, C, seed=3), dense.windows(B, T, F, seed=0), F, C)
+    print("max rel %.3g at l_b %.3g; l_b up to %.3g" % (rel.max(), loss[rel.argmax()], loss.max()))
     assert rel.max() <= 1e-6
 
 
