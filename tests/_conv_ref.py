@@ -83,6 +83,18 @@ bound_act16, which the half ulp of the stored rounding leads: a truncation inste
 to nearest, or a double rounding, would break it.  On small magnitudes (1e-5 .. 1e-3, K = 16) the
 emulation reaches 0.62 of the bound and 59.6 times the bound without its 2^-25 B' term.
 
+The sharp statistic (nerr_rms, yardstick).  The headroom above is the bounds' blind
+spot: gamma(3 K + 2) A grows like K, the honest error like sqrt(K), and the error of a lost lo
+product (2^-12 relative per term, signs at random) shrinks like 1 / sqrt(K) against A.  At K = 216
+"drop wh xl everywhere" is 1.8 x bound_x3; at K = 1620 it is 0.11, at K = 2304 0.06; for wino2,
+"drop Uh Vl in one of the 16 GEMMs" at cin 512 is 0.06 of bound_wino2.  The rms over a tensor of
+d / A (d / A_wino) does not have that slope: 1.15e-8 .. 1.18e-8 for emu_wino2 at cin 128 .. 512 and
+3.0e-8 .. 3.2e-8 for emu_x3 at K 512 .. 2304, whatever the order of the sum; a float32 convolution
+and a pairwise sum per 16 channels sit at 0.1 .. 0.4 of it.  So a kernel's output is held, per
+(frame, 32 output channels), to NERR_FACTOR = 3 times E, the same figure of the emulation on the
+case's own inputs -- the reference arithmetic is the yardstick, never the kernel.  Every mutant of
+lo_mutant() tried is at 15 E or more at every depth (test_conv_ref.py::test_statistic_is_sharp).
+
 The bound is not vacuous for being loose in the sum: it is per element and normalised by A there,
 where the whole-net bar max |d| / max |ref| < 1e-4 is one number per tensor.  The mutation checks of
 test_conv_ref.py (a dropped corner tap, a skipped chunk pair of one channel, two channels swapped,
@@ -199,11 +211,12 @@ def act_factor(slope, act):
     return 1.0
 
 
-def bound_x3(x, w, b, slope=None, act="none", abs_term=True):
+def bound_x3(x, w, b, slope=None, act="none", abs_term=True, A=None):
     """Three-term conv_x3 / conv_x3_rgb against ref64(x, w, b).  abs_term=False drops the
-    2^-25 B' term (the small-magnitude test shows it is needed)."""
+    2^-25 B' term (the small-magnitude test shows it is needed).  A: absum(x, w, b) where the
+    caller has it."""
     K = w.shape[1] * w.shape[2] * w.shape[3]
-    A = absum(x, w, b)
+    A = absum(x, w, b) if A is None else A
     e = gamma(3 * K + 2) * (1 + 2.0 ** -9) * A + C_S * 2.0 ** -21 * A
     if abs_term:
         Bp = wsum(w, x.shape[2], x.shape[3]) + np.ldexp(1.0, -pack_exp(w)) * xsum(x, w.shape[2])
@@ -275,15 +288,31 @@ def wino_sums(x, w, b):
     return Aw, Aw2, Bw, Xw, s
 
 
+def wino_absum(x, w, b):
+    """A_wino alone (wino_sums()[0]): the yardstick of nerr_rms for the Winograd kernels."""
+    U = np.abs(np.einsum("ik,ockl,jl->ocij", _G, np.asarray(w, np.float64), _G))
+    V = np.abs(np.einsum("ik,ncabkl,jl->ncabij", _BT, _tiles(np.asarray(x, np.float64)), _BT))
+    aA = np.abs(_AT)
+    M = np.einsum("ik,noabkl,jl->noabij", aA, np.einsum("ocij,ncabij->noabij", U, V), aA)
+    return _untile(M, x.shape[2], x.shape[3]) + np.abs(np.asarray(b, np.float64))[None, :, None, None]
+
+
+def wino_exp(w):
+    """pack_wino_f16's s: max |U| 2^s in [2^13, 2^14) (0 for an all-zero filter)."""
+    mx = float(np.max(np.abs(np.einsum("ik,ockl,jl->ocij", _G, np.asarray(w, np.float64), _G))))
+    return 0 if mx == 0.0 else 14 - int(np.frexp(mx)[1])
+
+
 def bound_wino(x, w, b, slope=None, act="none"):
     cin = w.shape[1]
     Aw, Aw2, _, _, _ = wino_sums(x, w, b)
     return act_factor(slope, act) * (gamma(2 * cin + 7) * Aw + gamma(2) * (1 + 2.0 ** -10) * Aw2)
 
 
-def bound_wino2(x, w, b, slope=None, act="none"):
+def bound_wino2(x, w, b, slope=None, act="none", sums=None):
+    """sums: wino_sums(x, w, b) where the caller has it."""
     cin = w.shape[1]
-    Aw, Aw2, Bw, Xw, s = wino_sums(x, w, b)
+    Aw, Aw2, Bw, Xw, s = wino_sums(x, w, b) if sums is None else sums
     e = (gamma(3 * cin + 7) * (1 + 2.0 ** -9) * Aw + C_S * 2.0 ** -21 * Aw + gamma(2) * (1 + 2.0 ** -10) * Aw2 +
          C_U * 2.0 ** -25 * (Bw + np.ldexp(1.0, -s) * Xw))
     return act_factor(slope, act) * e
@@ -316,25 +345,87 @@ def _epilogue(acc, scale_inv, b, slope, act, shape):
     return np.ascontiguousarray(v, np.float32)
 
 
-def emu_x3(x, w, b, slope=None, act="none", seed=0, terms=3):
+# A mutant of the emulations: the arithmetic with one lo product removed or altered in one place,
+# as a K-loop rewrite loses or mixes up a fragment.  "hi lo" is (filter hi) x (activation lo):
+# wh xl, Uh Vl; "lo hi" is wl xh, Ul Vh.
+#   drop_hl / drop_lh   the product is left out
+#   one_term            both lo products are left out (what is left there is the one-term sum)
+#   stale_lo            the filters' lo fragment of chunk pair k (16 channels) is that of pair k - 1
+#                       (a filter register set that was not reloaded); pair 0 keeps its own
+# restricted to the input channels ci = (from, to), the output channels co = (from, to), one
+# Winograd GEMM xi = 4 i + j (emu_wino2) or one filter tap = ky ks + kx (emu_x3); None: everywhere.
+MUTANT_KINDS = ("drop_hl", "drop_lh", "one_term", "stale_lo")
+ORDERS = ("inorder", "shuffled", "tree16")
+
+
+def lo_mutant(kind, ci=None, co=None, xi=None, tap=None):
+    assert kind in MUTANT_KINDS
+    return dict(kind=kind, ci=ci, co=co, xi=xi, tap=tap)
+
+
+def _mutant_filters(m, Fh, Fl, inner):
+    """(the hi filters of the hi lo product, the lo filters of the lo hi product) of a mutant;
+    Fh, Fl [cout, cin, a, a], inner the (i, j) the mutant is restricted to or None."""
+    hit = np.zeros(Fh.shape, bool)
+    co = slice(None) if m["co"] is None else slice(*m["co"])
+    ci = slice(None) if m["ci"] is None else slice(*m["ci"])
+    hit[(co, ci) + ((slice(None), slice(None)) if inner is None else inner)] = True
+    assert hit.any()
+    zero = np.float32(0)
+    Fh_hl = np.where(hit, zero, Fh) if m["kind"] in ("drop_hl", "one_term") else Fh
+    Fl_lh = np.where(hit, zero, Fl) if m["kind"] in ("drop_lh", "one_term") else Fl
+    if m["kind"] == "stale_lo":
+        stale = Fl.copy()
+        stale[:, 16:] = Fl[:, :-16]
+        Fl_lh = np.where(hit, stale, Fl)
+    return Fh_hl, Fl_lh
+
+
+def _tree(P):
+    """The pairwise sum over axis 0 in float32 (an odd one out moves up a level unchanged)."""
+    while P.shape[0] > 1:
+        half = P.shape[0] // 2
+        head = P[0:2 * half:2] + P[1:2 * half:2]
+        P = head if P.shape[0] % 2 == 0 else np.concatenate([head, P[-1:]])
+    return P[0]
+
+
+def emu_x3(x, w, b, slope=None, act="none", seed=0, terms=3, mutant=None, order="shuffled", s=None):
     """The split arithmetic in numpy: fp16 hi / lo of x, fp16 hi / lo of w 2^s, the three exact
     products of every (tap, channel) added one by one into a float32 accumulator in a shuffled
-    order, the epilogue's 2^-s, bias and activation in float32.  terms=1: the one-term mode."""
+    order, the epilogue's 2^-s, bias and activation in float32.  terms=1: the one-term mode.
+    mutant: a lo_mutant() (three terms).  order: "shuffled" (by seed), "inorder" (k = (ci, ky, kx),
+    hi hi, lo hi, hi lo of each), "tree16" (the products of 16 channels summed pairwise, the
+    blocks' sums added in order: a matrix core's step).  s: the filters' exponent where it is not
+    that of w (a subset of a layer's output channels)."""
+    assert order in ORDERS and (mutant is None or terms == 3)
     x, w = np.asarray(x, np.float32), np.asarray(w, np.float32)
     n, cin, h, wd = x.shape
     cout, ks = w.shape[0], w.shape[2]
-    s = pack_exp(w)
+    s = pack_exp(w) if s is None else s
     ws = np.ldexp(w, s).astype(np.float32).reshape(cout, -1)
     wh = f16(ws)
     wl = f16(ws - wh)
     X = _im2col(x, ks)
     xh = f16(X)
     xl = f16(X - xh)
-    ops = [(wh, xh)] if terms == 1 else [(wh, xh), (wl, xh), (wh, xl)]
-    order = [(k, t) for k in range(X.shape[0]) for t in range(len(ops))]
-    np.random.default_rng(seed).shuffle(order)
+    wh_hl, wl_lh = wh, wl
+    if mutant is not None:
+        tap = None if mutant["tap"] is None else divmod(mutant["tap"], ks)
+        wh_hl, wl_lh = (f.reshape(cout, -1) for f in _mutant_filters(
+            mutant, wh.reshape(w.shape), wl.reshape(w.shape), tap))
+    ops = [(wh, xh)] if terms == 1 else [(wh, xh), (wl_lh, xh), (wh_hl, xl)]
     acc = np.zeros((cout, X.shape[1]), np.float32)
-    for k, t in order:
+    if order == "tree16":
+        kk = ks * ks
+        for c0 in range(0, cin, 16):
+            ksel = range(c0 * kk, min(c0 + 16, cin) * kk)
+            acc += _tree(np.stack([a[:, k, None] * v[None, k, :] for k in ksel for a, v in ops]))
+        return _epilogue(acc, np.ldexp(1.0, -s), b, slope, act, (n, cout, h, wd))
+    seq = [(k, t) for k in range(X.shape[0]) for t in range(len(ops))]
+    if order == "shuffled":
+        np.random.default_rng(seed).shuffle(seq)
+    for k, t in seq:
         a, v = ops[t]
         acc += a[:, k, None] * v[None, k, :]      # the product is exact in fp32, the += rounds
     return _epilogue(acc, np.ldexp(1.0, -s), b, slope, act, (n, cout, h, wd))
@@ -374,7 +465,8 @@ def emu_wino32(x, w, b, slope=None, act="none"):
 GUARD_CHECKS = ("pre_and_stored", "stored_only")
 
 
-def emu_wino2(x, w, b, slope=None, act="none", terms=3, check="pre_and_stored"):
+def emu_wino2(x, w, b, slope=None, act="none", terms=3, check="pre_and_stored", mutant=None, order="inorder", seed=0,
+              s=None):
     """csrc/wino_f16.hip in numpy, returning (y, flag).  U = G g G^T in float64, x 2^s, rounded to
     fp32, hi = fp16(U), lo = fp16(U - hi) (pack_wino_f16).  V = B^T d B in fp32, rows then columns,
     then split as split_dw does: hi = fp16(V) by RNE, which overflows to +-inf from |V| >= 65520, and
@@ -383,17 +475,23 @@ def emu_wino2(x, w, b, slope=None, act="none", terms=3, check="pre_and_stored"):
     the activation as the kernel writes it (v > 0 ? v : 0 -- a NaN becomes 0).
     check: where the range test sits.  "pre_and_stored": a non-finite value before the activation
     or a stored |v| outside [0, 65504) raises the flag (the kernel); "stored_only": the stored
-    value alone (the kernel before the ReLU hole was closed: GUARD_MUTATIONS)."""
-    assert check in GUARD_CHECKS and terms in (1, 3)
+    value alone (the kernel before the ReLU hole was closed: GUARD_MUTATIONS).
+    mutant, order, seed, s: as emu_x3 has them; the default order is the channels' own, with
+    Uh Vh, Uh Vl, Ul Vh of each."""
+    assert check in GUARD_CHECKS and terms in (1, 3) and order in ORDERS and (mutant is None or terms == 3)
     x = np.asarray(x, np.float32)
     n, cin, h, wd = x.shape
     cout = w.shape[0]
     U = np.einsum("ik,ockl,jl->ocij", _G, np.asarray(w, np.float64), _G)
     mx = float(np.max(np.abs(U)))
-    s = 0 if mx == 0.0 else 14 - int(np.frexp(mx)[1])
+    if s is None:
+        s = 0 if mx == 0.0 else 14 - int(np.frexp(mx)[1])
     Us = np.ldexp(U, s).astype(np.float32)
     Uh = f16(Us)
     Ul = f16(Us - Uh)
+    Uh_hl, Ul_lh = Uh, Ul
+    if mutant is not None:
+        Uh_hl, Ul_lh = _mutant_filters(mutant, Uh, Ul, None if mutant["xi"] is None else divmod(mutant["xi"], 4))
     d = _tiles(x, np.float32)
     bt = _BT.astype(np.float32)
     with np.errstate(over="ignore", invalid="ignore"):
@@ -408,11 +506,18 @@ def emu_wino2(x, w, b, slope=None, act="none", terms=3, check="pre_and_stored"):
         Vh = f16(V)                                      # +-inf from |V| >= 65520
         Vl = f16(V - Vh)                                 # -+inf beside an infinite hi
         M = np.zeros((n, cout) + d.shape[2:], np.float32)
-        for c in range(cin):
-            M += Uh[None, :, c, None, None] * Vh[:, None, c]
-            if terms == 3:
-                M += Uh[None, :, c, None, None] * Vl[:, None, c]
-                M += Ul[None, :, c, None, None] * Vh[:, None, c]
+        ops = [(Uh, Vh)] if terms == 1 else [(Uh, Vh), (Uh_hl, Vl), (Ul_lh, Vh)]
+        if order == "tree16":
+            for c0 in range(0, cin, 16):
+                M += _tree(np.stack([a[None, :, c, None, None] * v[:, None, c]
+                                     for c in range(c0, min(c0 + 16, cin)) for a, v in ops]))
+        else:
+            seq = [(c, t) for c in range(cin) for t in range(len(ops))]
+            if order == "shuffled":
+                np.random.default_rng(seed).shuffle(seq)
+            for c, t in seq:
+                a, v = ops[t]
+                M += a[None, :, c, None, None] * v[:, None, c]
         R0 = (M[..., 0, :] + M[..., 1, :]) + M[..., 2, :]
         R1 = (M[..., 1, :] - M[..., 2, :]) - M[..., 3, :]
         Y = np.empty(M.shape[:4] + (2, 2), np.float32)
@@ -535,6 +640,59 @@ def worst(y, ref, bound):
     r = np.where(np.isnan(r), np.inf, r)             # a NaN in y is no pass
     i = np.unravel_index(int(np.argmax(r)), r.shape)
     return float(r[i]), tuple(int(v) for v in i)
+
+
+# ---- the sharp statistic: the rms of the normalised error ------------------------------------
+# worst() against a gamma(3 K) bound grows blind with K (the docstring of test_conv_ref.py's
+# deep-K tests has the figures); the rms over a tensor of d / A is flat in K for the honest
+# arithmetic and moves 15 to 1000 times when one lo product is lost.
+
+NERR_GROUP = 32       # output channels per group: wino_f16's epilogue round, conv_x3's narrowest tile
+NERR_FACTOR = 3.0     # the bar is NERR_FACTOR x the emulation's own pooled figure (yardstick)
+
+
+def nerr_rms(y, ref, A, act_fac=1.0, groups=NERR_GROUP):
+    """The root mean square of |y - ref| / (act_fac A), in float64, per (frame, `groups`
+    consecutive output channels): [n, ceil(cout / groups)].  groups=None: one number for the
+    whole tensor.  A is absum() for the direct-form kernels and A_wino (wino_absum) for the
+    Winograd ones.  Elements with A == 0 are left out of the mean and must have d == 0; one that
+    has not, or a NaN in y, makes its group infinite."""
+    y = np.asarray(y, np.float64)
+    d = np.abs(y - ref)
+    A = np.broadcast_to(np.asarray(A, np.float64), d.shape)
+    fac = np.broadcast_to(np.asarray(act_fac, np.float64), d.shape)
+    live = A > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(live, d / (fac * A), 0.0) ** 2
+    bad = np.isnan(y) | (~live & (d != 0))
+
+    def rms(sl):
+        if bool(bad[sl].any()) or not bool(np.all(np.isfinite(q[sl]))):
+            return np.inf
+        return float(np.sqrt(q[sl].sum() / max(int(live[sl].sum()), 1)))
+    if groups is None:
+        return rms(np.s_[:])
+    n, c = d.shape[:2]
+    return np.array([[rms(np.s_[f, g:g + groups]) for g in range(0, c, groups)] for f in range(n)])
+
+
+def yardstick_channels(cout):
+    """The output channels the yardstick is computed on: the first 16 and the last 16."""
+    return np.unique(np.r_[0:min(16, cout), max(0, cout - 16):cout])
+
+
+def yardstick(kernel, x, w, b, slope=None, act="none"):
+    """E: the pooled nerr_rms of the reference arithmetic itself -- emu_wino2 for "wino2", emu_x3
+    for "x3" and "rgb" -- on the first frame and yardstick_channels() of a case's inputs, with the
+    whole layer's filter exponent.  Every group of a kernel's output is held to NERR_FACTOR x E."""
+    sel = yardstick_channels(w.shape[0])
+    x1, ws, bs = x[:1], w[sel], np.asarray(b)[sel]
+    ss = None if slope is None else np.asarray(slope)[sel]
+    if kernel == "wino2":
+        y, A = emu_wino2(x1, ws, bs, ss, act, s=wino_exp(w))[0], wino_absum(x1, ws, bs)
+    else:
+        y, A = emu_x3(x1, ws, bs, ss, act, s=pack_exp(w)), absum(x1, ws, bs)
+    return nerr_rms(y, ref64(x1, ws, bs, ss, None, act), A, act_factor(ss, act), None)
 
 
 # ---- mutations: references that are wrong in one local way ----------------------------------

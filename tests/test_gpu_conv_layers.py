@@ -10,7 +10,15 @@ built to reach one variant of the dispatch and is held to
   f) the range guard: a layer is within its bound or raises the flag -- at an output
      (test_range_guard), at an intermediate while every input and output is in range
      (test_range_guard_transform: the Winograd input transform), and on in-contract inputs of
-     large magnitude for one case per kernel family (test_flag_or_bound).
+     large magnitude for one case per kernel family (test_flag_or_bound),
+  g) the sharp statistic, for the three-term form of every x3, rgb and wino2 case: the rms of
+     |d| / A (A_wino for wino2) over each (frame, 32 output channels) is at most 3 E, E being the
+     same figure of the numpy emulation of that arithmetic on the case's own inputs
+     (cr.yardstick).  The bound of (a) carries gamma(3 K) and goes blind with K: a kernel that
+     loses one of its three products passes it from K ~ 1000 on.  This one is flat in K (CPU proof:
+     tests/test_conv_ref.py); the deep cases (wino2-c128 .. c512, union-k2304, pairs2-k512) put
+     it at the depths the nets run.  The one-term and fp16-storage forms are exempt (their
+     references isolate the summation already), direct and wino are the fp32 controls.
 Runs on an MI355X only (-m gpu)."""
 import contextlib
 import os
@@ -116,6 +124,15 @@ CASES = [
     case("wino2-19x65", "k3.p128.c64.w2", 3, 40, 128, 2, 19, 65, kernel="wino2", lone=True, out_coff=8, out_cs=144, out_pad=3,
          family="postact"),
     case("wino2-small", "k3.p128.c64.w2", 3, 16, 64, 1, 17, 63, kernel="wino2", family="small", act="none"),
+    # -- the depths the nets run (assertion g): the smallest planes launch_wino_f16 takes
+    case("wino2-c128", "k3.p128.c64.w2", 3, 128, 256, 2, 17, 63, kernel="wino2", lone=True),   # 4 channel blocks; 288 tiles: a half-full last block
+    case("wino2-c180", "k3.p128.c64.w2", 3, 180, 128, 2, 19, 65, kernel="wino2", act="relu", segs=C180),   # 23 chunks: no odd chunk in the last pair; TW = 33
+    case("wino2-c256", "k3.p128.c64.w2", 3, 256, 128, 3, 20, 64, kernel="wino2", act="none", out_pad=3),   # whole tiles, bands and blocks: the control
+    case("wino2-c384", "k3.p128.c64.w2", 3, 384, 128, 1, 18, 64, kernel="wino2", in_coff=8, in_cs=400, out_coff=128, out_cs=384),   # a slice into a slot; 9 tile rows
+    case("wino2-c512", "k3.p128.c64.w2", 3, 512, 192, 1, 17, 63, kernel="wino2", family="postact"),   # 32 pairs; 3 channel blocks
+    # ... and of the 512-pixel family: 128 x 2 tiles = 256 blocks, the smallest batch with these planes
+    case("union-k2304", "k3.p512.c128.union", 3, 256, 128, 128, 27, 19),                  # 513 px: a one-pixel tail tile
+    case("pairs2-k512", "k1.p256.c256.pairs2", 1, 512, 256, 128, 9, 29, act="relu"),      # 261 px: a five-pixel tail tile
     case("direct-k1", "none", 1, 24, 26, 2, 9, 13, kernel="direct"),
     case("direct-k3", "none", 3, 180, 52, 2, 9, 13, kernel="direct", segs=C180, in_coff=16, out_coff=8, out_cs=72),
     case("direct-k7", "none", 7, 16, 128, 2, 9, 9, kernel="direct", act="relu"),
@@ -186,16 +203,30 @@ def inputs(c):
     return x, wt, b, s
 
 
-def reference(c, form, x, wt, b, s):
-    """(ref, bound) of a case in one of its forms."""
+SHARP = ("x3", "rgb", "wino2")     # the kernels whose three-term form assertion (g) holds to 3 E
+
+
+def reference(c, form, x, wt, b, s, sharp=None):
+    """(ref, bound) of a case in one of its forms.  sharp: a dict that receives what assertion
+    (g) needs of a three-term x3, rgb or wino2 case: A (absum, or A_wino for wino2) and the
+    yardstick E of the reference arithmetic (cr.yardstick)."""
     k, act = c["kernel"], c["act"]
     if form:                                        # one-term: ref64 of the rounded operands
         xr, wr = cr.f16(x), cr.round_w_f16(wt)
         ref, bound = cr.ref64(xr, wr, b, s, c["ks"], act), cr.bound_f16(xr, wr, b, s, act)
         return (ref, cr.bound_act16(bound, ref)) if form == "a16" else (ref, bound)
     ref = cr.ref64(x, wt, b, s, c["ks"], act)
-    fn = {"x3": cr.bound_x3, "rgb": cr.bound_x3, "direct": cr.bound_direct, "wino": cr.bound_wino, "wino2": cr.bound_wino2}[k]
-    return ref, fn(x, wt, b, s, act)
+    if k == "wino2":
+        sums = cr.wino_sums(x, wt, b)
+        A, bound = sums[0], cr.bound_wino2(x, wt, b, s, act, sums=sums)
+    elif k in ("x3", "rgb"):
+        A = cr.absum(x, wt, b)
+        bound = cr.bound_x3(x, wt, b, s, act, A=A)
+    else:
+        A, bound = None, {"direct": cr.bound_direct, "wino": cr.bound_wino}[k](x, wt, b, s, act)
+    if sharp is not None and k in SHARP:
+        sharp.update(A=A, E=cr.yardstick(k, x, wt, b, s if act == "prelu" else None, act))
+    return ref, bound
 
 
 def launch(c, form, x, wt, b, s, **more):
@@ -215,6 +246,17 @@ REACHED = set()       # the variant names the tests of this file launched
 KEPT = {}             # three-term results other tests compare against: name -> DebugConvResult
 
 
+def case_reference(c, form, x, wt, b, s):
+    """(ref, bound, sharp) of a case's form, computed once for the cases that share its inputs
+    (the two sides of a switch): the float64 reference is each case's host time."""
+    def make():
+        sharp = {}
+        return reference(c, form, x, wt, b, s, sharp) + (sharp,)
+    if sum(o["data"] == c["data"] for o in CASES) == 1:          # nobody to share with: nothing kept
+        return make()
+    return shared(("layer", c["data"], form, c["kernel"], c["act"]), make)
+
+
 def run(c, form):
     """A case's runs: the layer twice, the last frame alone, reference and bound."""
     x, wt, b, s = inputs(c)
@@ -224,9 +266,9 @@ def run(c, form):
     # one-term form, whose values the fp16-storage form stores rounded)
     lone_form = "f16" if form == "a16" and c["kw"].get("allow_split") else form
     last = launch(c, lone_form, x[-1:], wt, b, s) if c["lone"] and c["n"] > 1 else None
-    ref, bound = reference(c, form, x, wt, b, s)
+    ref, bound, sharp = case_reference(c, form, x, wt, b, s)
     REACHED.add(vname(a.variant))
-    return dict(a=a, again=again, last=last, ref=ref, bound=bound)
+    return dict(a=a, again=again, last=last, ref=ref, bound=bound, sharp=sharp, fac=cr.act_factor(s, c["act"]))
 
 
 def kept(name):
@@ -260,6 +302,14 @@ def test_layer(c, form):
         clean(r["last"])
         last = cr.f16(r["last"].y) if form == "a16" and not rt.decode_variant(r["last"].variant)["act16"] else r["last"].y
         assert np.array_equal(a.y[-1:].view(np.uint32), last.view(np.uint32))
+    if r["sharp"]:                                                                 # g
+        E = r["sharp"]["E"]
+        groups = cr.nerr_rms(a.y, r["ref"], r["sharp"]["A"], r["fac"])
+        f, g = (int(v) for v in np.unravel_index(int(np.argmax(groups)), groups.shape))
+        print("%s: largest group nerr_rms %.3e = %.3f of the bar 3 E (E %.3e), frame %d channels %d..%d" % (
+            c["name"], groups[f, g], groups[f, g] / max(cr.NERR_FACTOR * E, 1e-300), E, f, cr.NERR_GROUP * g,
+            min(cr.NERR_GROUP * (g + 1), c["cout"]) - 1))
+        assert np.all(groups <= cr.NERR_FACTOR * E)
 
 
 # "Same bits" the source states between two sides of a per-launch switch (csrc/conv_x3.hip: the

@@ -81,6 +81,22 @@ def test_table_is_closed_under_the_decision(tool):
     assert m and int(m.group(1)) > 1000000 and int(m.group(2)) > 60, r.stdout
 
 
+# The deep-K cases of tests/test_gpu_conv_layers.py (union-k2304, pairs2-k512): the launch, the
+# choice it must get, and the choice one frame fewer gets (255 blocks: the 512-pixel row union and
+# the 256-channel tiles need a grid of 256).
+DEEP_K = [("ks=3 cin_chunks=32 cout=128 bco=128 n=%d H=27 W=19 in_pad=1", "f16<3,2,8,2,2,512,4> S=1 x=0", "f16<3,2,4,2,1,0,2> S=1 x=0"),
+          ("ks=1 cin_chunks=64 cout=256 bco=256 n=%d H=9 W=29 in_pad=1", "f16<1,4,4,2,2,4096,1> S=1 x=0", "none")]
+
+
+@pytest.mark.parametrize("desc,at128,at127", DEEP_K, ids=["union-k2304", "pairs2-k512"])
+def test_deep_k_cases_take_the_smallest_batch(tool, tmp_path, desc, at128, at127):
+    q = tmp_path / "q.txt"
+    q.write_text("".join("%s | |\n" % (desc % n) for n in (128, 127)))
+    got = [ln.split("|")[2].strip() for ln in subprocess.run([tool, str(q), "256"], check=True, timeout=60, capture_output=True,
+                                                             text=True).stdout.splitlines()]
+    assert got[0].startswith(at128) and got[1].startswith(at127), got
+
+
 def test_switches_are_read_in_one_place():
     """getenv: in x3_select.cpp only inside x3_switches(), nowhere in conv_x3.hip."""
     with open(os.path.join(CSRC, "conv_x3.hip")) as f:
